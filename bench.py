@@ -13,6 +13,14 @@ barrier + torch.cuda.synchronize on both sides; per-step time is the MAX over
 ranks; value = ms_per_step * 50 / 1000 = end-to-end 50-step latency
 (output_type=latent protocol: VAE/text-encode excluded, as in the
 reference's run_sdxl.py benchmark mode).
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the K steps, print the result line. ``--dump-outputs DIR`` additionally
+writes what the last timed step returned (the latents) as DIR/latents.npy in
+float32; weights, prompt and initial latents are seeded, so the same
+arguments give the same inputs in every run and two builds can be compared
+output for output. ``--full`` is where every measurement beyond the headline
+figure belongs; today the benchmark has none, so it changes nothing yet.
 """
 
 from __future__ import annotations
@@ -22,8 +30,26 @@ import json
 import os
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
+
+DUMP_LIMIT_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(out_dir: str, outputs: dict[str, torch.Tensor]) -> None:
+    """Write each output as <out_dir>/<name>.npy in float32, at most
+    DUMP_LIMIT_BYTES in all; a larger output is cut down to a fixed, seeded
+    sample of its flattened elements (in index order)."""
+    os.makedirs(out_dir, exist_ok=True)
+    # float32 elements per array, leaving room for the .npy header
+    budget = (DUMP_LIMIT_BYTES // len(outputs) - 1024) // 4
+    for name, tensor in outputs.items():
+        arr = tensor.detach().float().cpu().numpy()
+        if arr.size > budget:
+            idx = np.random.default_rng(0).choice(arr.size, size=budget, replace=False)
+            arr = arr.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
 
 
 def main() -> None:
@@ -44,11 +70,21 @@ def main() -> None:
     ap.add_argument("--warmup-steps", type=int, default=4, help="sync-comm denoise steps")
     ap.add_argument("--preset", type=str, default="sdxl", choices=["sdxl", "tiny"],
                     help="tiny = CPU plumbing test of the distributed bench path")
+    ap.add_argument("--cpu", action="store_true",
+                    help="run on the CPU over gloo even where GPUs are present "
+                         "(plumbing tests with more ranks than GPUs)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline figure "
+                         "(none exist yet: same as a plain run)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from distrifuser_amd import DistriConfig, DistriSDXLPipeline
 
-    use_cuda = torch.cuda.is_available()
+    use_cuda = torch.cuda.is_available() and not args.cpu
     if use_cuda:
         # let MIOpen search for the best conv algorithm per shape (the
         # default immediate mode picked an im2col path for some 3840^2 convs
@@ -75,6 +111,7 @@ def main() -> None:
         mode=args.mode,
         parallelism=args.parallelism,
         use_cuda_graph=use_graphs,
+        **({"backend": "gloo", "device": "cpu"} if args.cpu else {}),
     )
     if cfg.world_size > 1:
         assert cfg.world_size == args.gpus, (
@@ -132,6 +169,10 @@ def main() -> None:
                          device=cfg.device if use_cuda else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs and cfg.rank == 0:
+        # every rank holds the full gathered latents; rank 0 writes them
+        dump_outputs(args.dump_outputs, {"latents": latents})
 
     ms_per_step = elapsed / args.steps * 1000.0
     latency_50 = ms_per_step * 50 / 1000.0
