@@ -2,30 +2,48 @@
 // §2.4a): rectangular local-query x global-(stale)-KV attention.
 //
 // Structure (cdna_hip_programming.md §B "8-warp 32x32 ladder"; evolution and
-// per-step measurements in profiles/attention_ladder_r01.md):
+// per-step measurements in profiles/attention_ladder_r01.md and
+// profiles/attention_r03_notes.md):
 // * 8-wave workgroup per (batch, head, 256-row Q tile); each wave owns 32 Q
 //   rows held in registers (4 k-slice A/B fragments). Q-block size governs
 //   KV re-read traffic (each KV tile is re-read Lq/QBLK times).
-// * KV streamed in 64-token LDS tiles shared by the waves; K row-major
-//   [64][64], V TRANSPOSED [d][t]; XOR swizzle byte^=((row&7)<<4) breaks the
-//   16-way bank conflict of row-major [.][64] bf16 tiles (guide §6 G4).
+// * KV streamed in 128-token LDS tiles shared by the waves. K and V are
+//   staged the same way: b128 global loads into a row-major [t][d] image,
+//   zero-filled beyond Dh and beyond Lkv. K rows are padded by 8 B; V rows
+//   are unpadded with a 64 B-granular XOR (v_swz) that keeps the transposed
+//   reads conflict-free.
+// * Full 128-token tiles run mask-free; one peeled tail tile handles
+//   Lkv % 128 (mask-free when the remainder is 64, per-element masked
+//   otherwise).
 // * SWAPPED QK^T: S^T = K_tile x Q^T via mfma_f32_32x32x16_bf16, so each
 //   lane holds 16 score rows of ONE q column (q = lane&31) — the online-
-//   softmax max/sum are 15 in-register ops + ONE shfl_xor(32) with the
-//   partner lane, instead of 30+ cross-lane shuffles per tile (guide
+//   softmax max/sum are 15 in-register ops + ONE permlane32_swap with the
+//   partner half, instead of 30+ cross-lane shuffles per tile (guide
 //   common-mistake #6 / §B "swapped QK^T").
-// * P stays in registers: v_cvt_pk_bf16_f32 packs + shfl_xor(32) partner
-//   exchange build the PV B-fragments directly (guide T12), no P LDS
-//   round-trip.
-// * PV is also swapped: O^T = V^T x P^T accumulates in 2x16 AGPRs per lane.
+// * P stays in registers: v_cvt_pk_bf16_f32 packs + 4 permlane32_swap per
+//   32-token sub-tile build the PV B-fragments directly (guide T12), no P LDS
+//   round-trip and no half select.
+// * PV is also swapped: O^T = V^T x P^T accumulates in 2x16 registers per
+//   lane; the V^T A-fragments come from the row-major V image through
+//   ds_read_b64_tr_b16 (guide T10), two per fragment.
 // * stale-KV chunking: KV tokens come from NC flat-comm-buffer chunks of LC
 //   tokens (k_sc/v_sc strides) — the displaced-patch KV is consumed in place
-//   with zero torch.cat.
+//   with zero torch.cat. The (chunk, token-in-chunk)
+//   position of the tile being staged is a wave-uniform cursor advanced per
+//   tile; every token row resolves its own chunk from it, so a tile may
+//   straddle chunk boundaries and the tile loop holds no division.
+// * SPLIT staging (guide T14): the next tile's global loads are issued into
+//   registers before the current tile's compute and written to LDS after the
+//   barrier that ends it; the barriers are raw s_barrier + lgkmcnt-only
+//   waits, so the loads stay in flight across them.
 //
 // Fragment maps (verified on MI355X by tests/test_ops_gpu.py probes):
 //   16x16x32: A[row=l&15][k=(l>>4)*8+j]  B[k][col=l&15]  D[row=(l>>4)*4+r][col=l&15]
 //   32x32x16: A[row=l&31][k=(l>>5)*8+j]  B[k][col=l&31]
 //             D[row=(r&3)+8*(r>>2)+4*(l>>5)][col=l&31]
+//   ds_read_b64_tr_b16, per 16-lane group: lane 4q+p supplies the address of
+//   block row q, columns 4p..4p+3; lane i receives column i, row q in
+//   element q.
 
 #include "common.h"
 #include "kernels.h"
@@ -33,48 +51,89 @@
 namespace {
 
 constexpr int QW = 32;     // q rows per wave
+constexpr int KVB = 128;   // kv tokens per LDS tile
+// split staging (issue-early / write-late) measured +1 % at L=57.6k and
+// +5-7 % on the chunked shapes against loading after the barrier
+constexpr bool SPLIT_STAGE = true;
 // waves per block is a template parameter: bigger Q blocks amortize the KV
 // stream (each KV tile is re-read Lq/QBLK times), smaller blocks keep small
 // Lq shapes filled. Measured: 4w->8w at L=57.6k was +53% (439->673 TF).
-// KVB (kv tokens per LDS tile) and DPAD (head_dim padded to a multiple of
-// 32) are template parameters: KVB=128 amortizes staging barriers, KVB=64
-// keeps Lkv % 128 == 64 shapes (SDXL's 14400-token stage) mask-free; DPAD
+// DPAD (head_dim padded to a multiple of 32) is a template parameter and
 // covers the SD-family head dims (SDXL/SD2: 64; SD1.5: 40->64, 80->96,
 // 160). The real head_dim rides in FlashAttnParams.Dh; padding lanes carry
 // zeros (exact for QK^T scores and O columns < Dh).
 
 typedef float float4v_ __attribute__((ext_vector_type(4)));
 typedef float float16v __attribute__((ext_vector_type(16)));
+typedef short short4v __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) short4v lds_short4v;
 
-template <int ROW_BYTES>
-__device__ __forceinline__ int vt_swz(int row, int byte_off) {
-    // XOR over all 16 B windows of a power-of-two LDS row: spreads same-
-    // column reads across banks (16 windows at 256 B rows is a free 2-way
-    // conflict per guide m136; 8 windows at 128 B rows is the 4-way floor)
-    static_assert((ROW_BYTES & (ROW_BYTES - 1)) == 0);
-    return byte_off ^ ((row & (ROW_BYTES / 16 - 1)) << 4);
+template <int DPAD>
+__device__ __forceinline__ int v_swz(int t) {
+    // One tr read takes, per 32-lane half, rows 4n..4n+3 of a 64 B column
+    // window. Conflict-free needs those four 64 B pieces in four different
+    // quarters of the 256 B bank row (guide §2). Rows of 192/320 B already
+    // step by 64 B (mod 256); 128 B rows need rows {4n,4n+1} and {4n+2,4n+3}
+    // told apart, 256 B rows need all four.
+    if constexpr (DPAD % 128 == 0)
+        return (t & 3) << 6;
+    else if constexpr (DPAD % 64 == 0)
+        return ((t >> 1) & 1) << 6;
+    else
+        return 0;
 }
 
 __device__ __forceinline__ uint32_t cvt_pk_bf16(float a, float b) {
     uint32_t r;
-    asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
 
-template <int NW, int DPAD, int KVB, bool MASK, bool DEFER>
-__global__ __launch_bounds__(NW * WAVE_SIZE) void flash_attn_kernel(FlashAttnParams p) {
+__device__ __forceinline__ void lds_barrier() {
+    // raw barrier with an LDS-only wait: unlike __syncthreads() it leaves
+    // outstanding global loads in flight (guide §5 "Pipelining across
+    // barriers")
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
+// lanes l and l^32 both end up with op(own, partner): one permlane32_swap of
+// a value with itself puts the lower half's value in r[0] and the upper
+// half's in r[1]. (The elements are copied to scalars first:
+// __builtin_bit_cast on r[1] itself reads element 0.)
+__device__ __forceinline__ float half_max(float v) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, v);
+    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    const uint32_t a = r[0], b = r[1];
+    return fmaxf(__builtin_bit_cast(float, a), __builtin_bit_cast(float, b));
+}
+__device__ __forceinline__ float half_sum(float v) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, v);
+    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    const uint32_t a = r[0], b = r[1];
+    return __builtin_bit_cast(float, a) + __builtin_bit_cast(float, b);
+}
+
+// head_dim 64 is held to 128 registers: two 8-wave blocks per CU
+template <int NW, int DPAD, bool SPLIT>
+__global__ __launch_bounds__(NW * WAVE_SIZE)
+__attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
+    FlashAttnParams p) {
+    constexpr int NT = NW * WAVE_SIZE;
     constexpr int QBLK = QW * NW;
-    constexpr int VT_ROW = KVB * 2;         // V^T LDS row bytes [d][t]
     // K rows padded by 8 B: row stride DPAD*2+8 gives gcd(stride/4, 32) = 2,
     // so the 32-consecutive-row column reads are 2-way (free) instead of the
     // 4-way floor of XOR-swizzled 128 B rows — same trick as the conv
     // kernel's staged tile (profiles/conv_ladder_r02.md v5). Reads/writes
     // are b64 pairs (rows are 8 B- but not 16 B-aligned).
     constexpr int K_ROW = DPAD * 2 + 8;     // padded K LDS row bytes [t][d]
+    constexpr int V_ROW = DPAD * 2;         // V LDS row bytes [t][d], v_swz'd
     constexpr int KS = DPAD / 16;           // QK^T k-slices
     constexpr int DT = DPAD / 32;           // PV / O^T d-tiles
-    __shared__ char k_lds[KVB * K_ROW];     // [t][d] bf16, padded rows
-    __shared__ char vt_lds[DPAD * VT_ROW];  // [d][t] bf16, swizzled rows
+    constexpr int KCOLS = DPAD / 8;         // 16 B pieces per K/V row
+    constexpr int NLD = KVB * KCOLS / NT;   // b128 loads per thread per tile, K and V each
+    static_assert(KVB * KCOLS % NT == 0);
+    __shared__ __attribute__((aligned(16))) char k_lds[KVB * K_ROW];
+    __shared__ __attribute__((aligned(16))) char v_lds[KVB * V_ROW];
 
     const int tid = threadIdx.x;
     const int wave = tid / WAVE_SIZE;
@@ -87,7 +146,8 @@ __global__ __launch_bounds__(NW * WAVE_SIZE) void flash_attn_kernel(FlashAttnPar
     const int h = bh % p.H;
     const int64_t q0 = (int64_t)blockIdx.x * QBLK;
 
-    const int64_t Lkv = p.NC * p.LC;
+    const int LC = (int)p.LC;
+    const int Lkv = (int)(p.NC * p.LC);
     const uint16_t* qbase = p.q + b * p.q_sb + h * p.q_sh;
     const uint16_t* kbase = p.k + b * p.k_sb + h * p.k_sh;
     const uint16_t* vbase = p.v + b * p.v_sb + h * p.v_sh;
@@ -109,13 +169,92 @@ __global__ __launch_bounds__(NW * WAVE_SIZE) void flash_attn_kernel(FlashAttnPar
         }
     }
 
+    // ---- V^T A-fragment read addresses: the tr read of 16-lane group g
+    // takes V rows t = tb + hi*8 + rr*4 + q (q = 0..3), columns
+    // d = dt*32 + (g&1)*16 + 0..15, so lane i of the group supplies the
+    // address of row q = i>>2, columns (g&1)*16 + (i&3)*4 .. +3 and receives
+    // d = dt*32 + (lane&31) — the MFMA A row. tb is a multiple of 16, so
+    // v_swz(t) depends on q alone and everything but this per-lane base is
+    // an immediate offset. ----
+    int vrd[DT];
+    {
+        const int i = lane & 15;
+        const int q = i >> 2;
+        const int col_b = ((lane >> 4) & 1) * 32 + (i & 3) * 8;
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt)
+            vrd[dt] = (hi * 8 + q) * V_ROW + ((dt * 64 + col_b) ^ v_swz<DPAD>(q));
+    }
+
+    // ---- staging: thread (t-row, 16 B column) moves one b128 piece of K and
+    // one of V per pass. cur_chunk/cur_tin locate the first token of the tile
+    // being loaded; tiles advance monotonically. ----
+    int cur_chunk = 0, cur_tin = 0;
+    uint4 kreg[NLD], vreg[NLD];
+    // piece i of this thread: linear index tid + i*NT over [KVB][KCOLS]. Where
+    // a pass covers whole rows the passes differ by a constant row step, which
+    // keeps every LDS write address one base plus an immediate.
+    auto stage_row = [&](int i) {
+        if constexpr (NT % KCOLS == 0)
+            return tid / KCOLS + i * (NT / KCOLS);
+        else
+            return (tid + i * NT) / KCOLS;
+    };
+    auto stage_col = [&](int i) {
+        if constexpr (NT % KCOLS == 0)
+            return tid % KCOLS;
+        else
+            return (tid + i * NT) % KCOLS;
+    };
+    auto stage_load = [&]<bool MASKED>(int t0) {
+#pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            const int t_local = stage_row(i);
+            const int d8 = stage_col(i);
+            int tin = cur_tin + t_local;
+            int ch = cur_chunk;
+            while (tin >= LC) {
+                tin -= LC;
+                ++ch;
+            }
+            kreg[i] = uint4{0, 0, 0, 0};
+            vreg[i] = uint4{0, 0, 0, 0};
+            const bool d_ok = (p.Dh == DPAD) || (d8 * 8 + 8 <= p.Dh);
+            if (d_ok && (!MASKED || t0 + t_local < Lkv)) {
+                kreg[i] = *reinterpret_cast<const uint4*>(
+                    kbase + ch * p.k_sc + tin * p.k_sl + d8 * 8);
+                vreg[i] = *reinterpret_cast<const uint4*>(
+                    vbase + ch * p.v_sc + tin * p.v_sl + d8 * 8);
+            }
+        }
+        cur_tin += KVB;
+        while (cur_tin >= LC) {
+            cur_tin -= LC;
+            ++cur_chunk;
+        }
+    };
+    auto stage_write = [&]() {
+#pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            const int t_local = stage_row(i);
+            const int d8 = stage_col(i);
+            char* kdst = &k_lds[t_local * K_ROW + d8 * 16];
+            *reinterpret_cast<uint2*>(kdst) = uint2{kreg[i].x, kreg[i].y};
+            *reinterpret_cast<uint2*>(kdst + 8) = uint2{kreg[i].z, kreg[i].w};
+            *reinterpret_cast<uint4*>(
+                &v_lds[t_local * V_ROW + ((d8 * 16) ^ v_swz<DPAD>(t_local))]) = vreg[i];
+        }
+    };
+
     // Online softmax bookkeeping (exp2 domain, guide §B):
     //   m_raw   running max of RAW scores (max commutes with the positive
     //           scale, so per-element work is p = exp2(fma(s, scale2, -msc))
     //           — ONE v_fma + ONE v_exp per score element)
     //   msc     m_raw * scale2 (refreshed only when m_raw moves)
     //   defer-max (guide T13): skip the O/l rescale while the tile max stays
-    //   within DEFER_THR (log2 units) of the running max
+    //   within DEFER_THR (log2 units) of the running max. The decision sits
+    //   before the exponentiation of the sub-tile it covers, and the previous
+    //   sub-tile's PV is already issued — nothing pending at the old max.
     float m_raw = -1e30f;
     float msc = -1e30f;
     float l_run = 0.f;
@@ -123,87 +262,34 @@ __global__ __launch_bounds__(NW * WAVE_SIZE) void flash_attn_kernel(FlashAttnPar
     const float scale2 = p.scale * 1.44269504088896340736f;
     const float defer_raw = 11.0f / scale2;
 
-    const int n_tiles = (int)((Lkv + KVB - 1) / KVB);
-    for (int tile = 0; tile < n_tiles; ++tile) {
-        const int64_t t0 = (int64_t)tile * KVB;
-        // ---- cooperative staging ----
-        // K [t][d]: thread (t-row, 16B column) -> b128 LDS write.
-        // V^T [d][t]: lane = d COLUMN, 8 consecutive tokens per pass — the
-        // global reads stay perfectly coalesced (64 lanes x 2B = one 128B row
-        // per token) and the LDS write becomes ONE b128 per lane instead of
-        // 8 scalar ds_write_b16 (the transpose-write conflicts were 15% of
-        // kernel time — see profiles/attention_ladder_r01.md ablation).
-        {
-            constexpr int KCOLS = DPAD / 8;  // 16 B chunks per K row
-            constexpr int NCHUNK = KVB * KCOLS;
+    // T15 att[2] double-pipeline (guide): while subtile st's softmax/PV
+    // runs on the VALU, subtile st+1's QK^T fills the OTHER score tile on
+    // the MFMA pipe (separate pipes -> free overlap). Static two-state
+    // ping-pong via full unroll (rule #20: no dynamic indexing).
+    auto qk_tile = [&](int st) {
+        float16v s = {};
+        __builtin_amdgcn_s_setprio(1);  // favor the MFMA wave (guide T5)
 #pragma unroll
-            for (int c = tid; c < NCHUNK; c += NW * WAVE_SIZE) {
-                const int t_local = c / KCOLS;
-                const int d8 = c % KCOLS;
-                const int64_t t_glob = t0 + t_local;
-                uint4 kraw = {0, 0, 0, 0};
-                const bool d_ok = (p.Dh == DPAD) || (d8 * 8 + 8 <= p.Dh);
-                if (d_ok && (!MASK || t_glob < Lkv)) {
-                    const int64_t chunk = t_glob / p.LC;
-                    const int64_t tin = t_glob % p.LC;
-                    kraw = *reinterpret_cast<const uint4*>(
-                        kbase + chunk * p.k_sc + tin * p.k_sl + d8 * 8);
-                }
-                char* kdst = &k_lds[t_local * K_ROW + d8 * 16];
-                *reinterpret_cast<uint2*>(kdst) = uint2{kraw.x, kraw.y};
-                *reinterpret_cast<uint2*>(kdst + 8) = uint2{kraw.z, kraw.w};
-            }
-            // V^T: wave w stages token rows [w*8, w*8+8) of each 8*NW-row pass
-            constexpr int VROWS_PER_PASS = NW * 8;
-#pragma unroll
-            for (int rep = 0; rep < KVB / VROWS_PER_PASS; ++rep) {
-                const int tb_local = rep * VROWS_PER_PASS + wave * 8;
-                const int64_t tb_glob = t0 + tb_local;
-                // tb_glob is a multiple of 8 and LC % 8 == 0 (host-checked),
-                // so the 8-token window lies in one chunk
-                const int64_t chunk = tb_glob / p.LC;
-                const int64_t tin = tb_glob % p.LC;
-                for (int d = lane; d < DPAD; d += WAVE_SIZE) {
-                    uint16_t ve[8];
-                    const uint16_t* vp = vbase + chunk * p.v_sc + tin * p.v_sl + d;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const bool ok = d < p.Dh && (!MASK || tb_glob + j < Lkv);
-                        ve[j] = ok ? vp[j * p.v_sl] : (uint16_t)0;
-                    }
-                    *reinterpret_cast<uint4*>(
-                        &vt_lds[d * VT_ROW + vt_swz<VT_ROW>(d, tb_local * 2)]) =
-                        *reinterpret_cast<const uint4*>(ve);
-                }
-            }
+        for (int ks = 0; ks < KS; ++ks) {
+            const int t = st * 32 + lo;
+            const char* ksrc = &k_lds[t * K_ROW + (ks * 16 + hi * 8) * 2];
+            const uint2 k0 = *reinterpret_cast<const uint2*>(ksrc);
+            const uint2 k1 = *reinterpret_cast<const uint2*>(ksrc + 8);
+            const uint4 kk{k0.x, k0.y, k1.x, k1.y};
+            const short8 kfrag = __builtin_bit_cast(short8, kk);
+            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfrag, qf[ks], s, 0, 0, 0);
         }
-        __syncthreads();
+        __builtin_amdgcn_s_setprio(0);
+        return s;
+    };
 
-        // T15 att[2] double-pipeline (guide): while subtile st's softmax/PV
-        // runs on the VALU, subtile st+1's QK^T fills the OTHER score tile on
-        // the MFMA pipe (separate pipes -> free overlap). Static two-state
-        // ping-pong via full unroll (rule #20: no dynamic indexing).
-        auto qk_tile = [&](int st) {
-            float16v s = {};
-            __builtin_amdgcn_s_setprio(1);  // favor the MFMA wave (guide T5)
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const int t = st * 32 + lo;
-                const char* ksrc = &k_lds[t * K_ROW + (ks * 16 + hi * 8) * 2];
-                const uint2 k0 = *reinterpret_cast<const uint2*>(ksrc);
-                const uint2 k1 = *reinterpret_cast<const uint2*>(ksrc + 8);
-                const uint4 kk{k0.x, k0.y, k1.x, k1.y};
-                const short8 kfrag = __builtin_bit_cast(short8, kk);
-                s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfrag, qf[ks], s, 0, 0, 0);
-            }
-            __builtin_amdgcn_s_setprio(0);
-            return s;
-        };
+    // one staged tile: NST 32-token sub-tiles, tokens >= Lkv masked if MASK
+    auto compute = [&]<int NST, bool MASK>(int t0) {
         float16v s_cur = qk_tile(0);
 #pragma unroll
-        for (int st = 0; st < KVB / 32; ++st) {  // 32-token sub-tiles
+        for (int st = 0; st < NST; ++st) {
             float16v s_nxt;
-            if (st + 1 < KVB / 32) s_nxt = qk_tile(st + 1);
+            if (st + 1 < NST) s_nxt = qk_tile(st + 1);
             const float16v s = s_cur;
             // lane holds S^T rows crow(r) = (r&3)+8*(r>>2)+4*hi for q col lo
             float tm = -1e30f;
@@ -218,9 +304,9 @@ __global__ __launch_bounds__(NW * WAVE_SIZE) void flash_attn_kernel(FlashAttnPar
                 pv[r] = v;
                 tm = fmaxf(tm, v);
             }
-            tm = fmaxf(tm, __shfl_xor(tm, 32, 64));  // partner holds the other 16 rows
+            tm = half_max(tm);  // partner holds the other 16 rows
 
-            if (!DEFER || __any(m_raw == -1e30f || tm > m_raw + defer_raw)) {
+            if (__any(m_raw == -1e30f || tm > m_raw + defer_raw)) {
                 const float m_new = fmaxf(m_raw, tm);
                 const float msc_new = m_new * scale2;
                 const float corr = __builtin_amdgcn_exp2f(msc - msc_new);
@@ -238,95 +324,132 @@ __global__ __launch_bounds__(NW * WAVE_SIZE) void flash_attn_kernel(FlashAttnPar
                 pv[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(pv[r], scale2, -msc));
                 tsum += pv[r];
             }
-            tsum += __shfl_xor(tsum, 32, 64);
-            l_run += tsum;
+            l_run += half_sum(tsum);
 
-            // ---- pack P to bf16 B-fragments (guide T12: cvt_pk + partner
-            // exchange); B frag j=0..7 -> P^T rows kt*16 + hi*8 + j ----
-            uint32_t w[8], wp[8];
+            // ---- pack P to bf16 B-fragments (guide T12: cvt_pk +
+            // permlane32_swap); B frag j=0..7 -> P^T rows kt*16 + hi*8 + j.
+            // Own word i holds regs {2i,2i+1} = rows {(2i&3)+8*(i>>1)+4*hi, +1}.
+            // swap(a, b) leaves a = {lower: a, upper: lower's b} and
+            // b = {lower: upper's a, upper: b}, so swapping word pairs 8 rows
+            // apart gives hi=0 rows 0..7 and hi=1 rows 8..15 in order. ----
+            uint32_t w[8];
 #pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                w[i] = cvt_pk_bf16(pv[2 * i], pv[2 * i + 1]);
-                wp[i] = __shfl_xor(w[i], 32, 64);
-            }
+            for (int i = 0; i < 8; ++i) w[i] = cvt_pk_bf16(pv[2 * i], pv[2 * i + 1]);
             short8 pb[2];
 #pragma unroll
             for (int kt = 0; kt < 2; ++kt) {
-                // own word i holds regs {2i,2i+1} = rows {(2i&3)+8*(2i>>2)+4*hi, +1};
-                // hi=0 needs [own 4kt,4kt+1 | partner 4kt,4kt+1], hi=1 the mirror.
-                uint32_t* pbw = reinterpret_cast<uint32_t*>(&pb[kt]);
-                if (hi == 0) {
-                    pbw[0] = w[4 * kt + 0];
-                    pbw[1] = w[4 * kt + 1];
-                    pbw[2] = wp[4 * kt + 0];
-                    pbw[3] = wp[4 * kt + 1];
-                } else {
-                    pbw[0] = wp[4 * kt + 2];
-                    pbw[1] = wp[4 * kt + 3];
-                    pbw[2] = w[4 * kt + 2];
-                    pbw[3] = w[4 * kt + 3];
-                }
+                const auto r0 = __builtin_amdgcn_permlane32_swap(w[4 * kt + 0], w[4 * kt + 2],
+                                                                 false, false);
+                const auto r1 = __builtin_amdgcn_permlane32_swap(w[4 * kt + 1], w[4 * kt + 3],
+                                                                 false, false);
+                const uint4 pw{r0[0], r1[0], r0[1], r1[1]};
+                pb[kt] = __builtin_bit_cast(short8, pw);
             }
 
-            // ---- O^T += V^T x P^T ----
+            // ---- O^T += V^T x P^T; A[d = lo][k = hi*8 + j] = V[t][d] with
+            // t = st*32 + kt*16 + hi*8 + j: two transposed 4-row reads ----
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt) {
 #pragma unroll
                 for (int kt = 0; kt < 2; ++kt) {
-                    const int d = dt * 32 + lo;
-                    short8 vf = *reinterpret_cast<const short8*>(
-                        &vt_lds[d * VT_ROW + vt_swz<VT_ROW>(d, (st * 32 + kt * 16 + hi * 8) * 2)]);
+                    const char* vsrc = &v_lds[vrd[dt] + (st * 32 + kt * 16) * V_ROW];
+                    const short4v v0 =
+                        __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4v*)vsrc);
+                    const short4v v1 =
+                        __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4v*)(vsrc + 4 * V_ROW));
+                    const short8 vf = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
                     ot[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pb[kt], ot[dt], 0, 0, 0);
                 }
             }
             __builtin_amdgcn_s_setprio(0);
             s_cur = s_nxt;
         }
-        __syncthreads();
-    }
+    };
 
-    // ---- epilogue: O[q][d] = O^T / l (only the real head_dim columns) ----
-    if (qvalid) {
-        const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
-        uint16_t* op = p.o + ((int64_t)b * p.Lq + qrow) * (p.H * p.Dh) + (int64_t)h * p.Dh;
+    // ---- tile loop: mask-free full tiles, then one peeled tail ----
+    const int n_full = Lkv / KVB;
+    const int rem = Lkv % KVB;
+    if (Lkv > 0) {
+        if (n_full > 0)
+            stage_load.template operator()<false>(0);
+        else
+            stage_load.template operator()<true>(0);
+        stage_write();
+        lds_barrier();
+    }
+    // Q has landed: without this the compiler cannot count the conditional
+    // loads behind the Q loads and drains the prefetch at the first QK^T
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only
+    for (int tile = 0; tile < n_full; ++tile) {
+        const int t0 = tile * KVB;
+        const bool next_full = tile + 1 < n_full;
+        auto load_next = [&]() {
+            if (next_full)
+                stage_load.template operator()<false>(t0 + KVB);
+            else if (rem)
+                stage_load.template operator()<true>(t0 + KVB);
+        };
+        if (SPLIT) load_next();
+        compute.template operator()<KVB / 32, false>(t0);
+        if (next_full || rem) {
+            lds_barrier();  // every wave is done reading this tile
+            if (!SPLIT) load_next();
+            stage_write();
+            lds_barrier();
+        }
+    }
+    if (rem == 64)
+        compute.template operator()<2, false>(n_full * KVB);
+    else if (rem)
+        compute.template operator()<KVB / 32, true>(n_full * KVB);
+
+    // ---- epilogue: O[q][d] = O^T / l (only the real head_dim columns).
+    // A lane holds 4 consecutive d per register group g (d = dt*32 + 8g +
+    // 4hi ..); swapping groups g and g+1 between the halves (guide T21)
+    // leaves each lane 8 consecutive d: one 16 B store instead of 8 shorts.
+    const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
+    uint16_t* op = p.o + ((int64_t)b * p.Lq + (qvalid ? qrow : 0)) * (p.H * p.Dh) +
+                   (int64_t)h * p.Dh;
 #pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
+    for (int dt = 0; dt < DT; ++dt) {
+        uint32_t ow[8];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int d = dt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                if (p.Dh == DPAD || d < p.Dh)
-                    op[d] = __builtin_bit_cast(uint16_t, __float2bfloat16(ot[dt][r] * inv));
-            }
+        for (int i = 0; i < 8; ++i) {
+            const uint32_t e0 =
+                __builtin_bit_cast(uint16_t, __float2bfloat16(ot[dt][2 * i] * inv));
+            const uint32_t e1 =
+                __builtin_bit_cast(uint16_t, __float2bfloat16(ot[dt][2 * i + 1] * inv));
+            ow[i] = e0 | (e1 << 16);
+        }
+#pragma unroll
+        for (int g = 0; g < 4; g += 2) {
+            const auto rx = __builtin_amdgcn_permlane32_swap(ow[2 * g], ow[2 * g + 2],
+                                                             false, false);
+            const auto ry = __builtin_amdgcn_permlane32_swap(ow[2 * g + 1], ow[2 * g + 3],
+                                                             false, false);
+            const int d0 = dt * 32 + 8 * (g + hi);
+            if (qvalid && (p.Dh == DPAD || d0 + 8 <= p.Dh))
+                *reinterpret_cast<uint4*>(op + d0) = uint4{rx[0], ry[0], rx[1], ry[1]};
+        }
     }
 }
 
 }  // namespace
 
-template <int NW, int DPAD, int KVB, bool MASK>
-static void launch_var(const FlashAttnParams& p, hipStream_t stream) {
+template <int DPAD>
+static void launch_dpad(const FlashAttnParams& p, hipStream_t stream) {
+    constexpr int NW = 8;
     const int qblk = QW * NW;
     dim3 grid((unsigned)((p.Lq + qblk - 1) / qblk), (unsigned)(p.B * p.H));
     dim3 block(NW * WAVE_SIZE);
-    flash_attn_kernel<NW, DPAD, KVB, MASK, true><<<grid, block, 0, stream>>>(p);
-}
-
-template <int DPAD>
-static void launch_dpad(const FlashAttnParams& p, hipStream_t stream) {
-    const int64_t Lkv = p.NC * p.LC;
-    if (Lkv % 128 == 0)
-        launch_var<8, DPAD, 128, false>(p, stream);
-    else if (Lkv % 64 == 0)
-        launch_var<8, DPAD, 64, false>(p, stream);
-    else
-        launch_var<8, DPAD, 128, true>(p, stream);
+    flash_attn_kernel<NW, DPAD, SPLIT_STAGE><<<grid, block, 0, stream>>>(p);
 }
 
 void launch_flash_attention_d64(const FlashAttnParams& p, hipStream_t stream) {
     // 8-wave (256-row) blocks measured best across the SD-family shapes;
-    // KVB prefers 128-token tiles when the sequence tiles evenly, else 64
-    // (still mask-free for Lkv % 64 == 0, e.g. SDXL's 14400-token stage),
-    // else the masked variant. DPAD covers the SD-family head dims.
+    // every Lkv takes 128-token tiles plus a peeled tail. DPAD covers the
+    // SD-family head dims.
     if (p.Dh <= 64)
         launch_dpad<64>(p, stream);
     else if (p.Dh <= 96)
