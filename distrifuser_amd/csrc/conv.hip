@@ -130,12 +130,18 @@ __global__ __launch_bounds__(YB * XW * WAVE_SIZE) void conv3x3_kernel(Conv3x3Par
 
     // ---- v7 staging prologue: per-slab state hoisted out of the k-loop.
     // Interior slabs load through a buffer descriptor whose num_records
-    // (= Cin * sc * 2 B) zeroes the cin tail in hardware, so the hot loop
-    // has no per-lane masks and no 64-bit address math (the v6 staging asm
-    // was saveexec/mad_i64-bound: ~21 us per 120 KB tile).
+    // zeroes the cin tail in hardware, so the hot loop has no per-lane
+    // masks and no 64-bit address math (the v6 staging asm was
+    // saveexec/mad_i64-bound: ~21 us per 120 KB tile). The range ends with
+    // the last row of the last channel, ((Cin-1) * sc + H * W) * 2 B, not at
+    // Cin * sc: for a row-band or channel-slice view (sc > H * W) the
+    // windows right of W in the last rows would otherwise read past the
+    // view, and past the allocation when the view ends it. Those elements
+    // are masked (tail_mask) or unused (xi >= XIN) either way.
     const int gr = (lane & 3) | ((lane & 8) >> 1);
     const int gw = ((lane >> 2) & 1) | (((lane >> 4) & 3) << 1);
-    const int32x4_ck desc0 = make_srsrc(xin, (uint32_t)((int64_t)p.Cin * p.x_sc * 2));
+    const int32x4_ck desc0 = make_srsrc(
+        xin, (uint32_t)(((int64_t)(p.Cin - 1) * p.x_sc + (int64_t)p.H * p.W) * 2));
     const uint32_t voff_inc = (uint32_t)(CIN_T * p.x_sc * 2);
     const bool w_vec = (p.W % 8) == 0;
     uint32_t voff[STRIP];

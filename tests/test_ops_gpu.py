@@ -1,5 +1,15 @@
 """GPU numerics: every gfx950 kernel vs the plain-PyTorch fp32 reference
-(ops/eager.py). Run on an MI355X box: pytest tests -m gpu -x -q"""
+(ops/eager.py), at randn inputs and a tolerance. The MFMA kernels have
+exact edge-shape suites of their own:
+* tests/test_attention_tiles_gpu.py: flash-attention tile structure;
+* tests/test_conv3x3_edges_gpu.py: conv3x3 with integer and impulse data,
+  bit-identical to float64 in all three launch configs (wide/small/stride 2,
+  vectorised and scalar staging, partial tiles, halo and strided views);
+* tests/test_vae_attention_edges_gpu.py: VAE attention as an exact row
+  gather at L around the 32-token tile, and peaked/stepped scores that pin
+  the tail mask, the split-K d-slices and the running-max rescale.
+
+Run on an MI355X box: pytest tests -m gpu -x -q"""
 
 import pytest
 import torch
