@@ -30,8 +30,14 @@
 //   tokens (k_sc/v_sc strides) — the displaced-patch KV is consumed in place
 //   with zero torch.cat. The (chunk, token-in-chunk)
 //   position of the tile being staged is a wave-uniform cursor advanced per
-//   tile; every token row resolves its own chunk from it, so a tile may
-//   straddle chunk boundaries and the tile loop holds no division.
+//   tile, together with a K and a V pointer at that token. A full tile that
+//   lies inside one chunk (a uniform compare) loads through a raw buffer
+//   descriptor seated at those pointers plus a lane offset computed once
+//   before the loop: no per-lane multiply, 64-bit arithmetic or exec-mask
+//   branch (head dims whose staging pass covers whole rows: DPAD 64, 128).
+//   Any other tile — one that straddles chunk boundaries, the tail, the
+//   other head dims — has every token row resolve its own chunk from the
+//   cursor; the tile loop holds no division either way.
 // * SPLIT staging (guide T14): the next tile's global loads are issued into
 //   registers before the current tile's compute and written to LDS after the
 //   barrier that ends it; the barriers are raw s_barrier + lgkmcnt-only
@@ -104,7 +110,11 @@ __device__ __forceinline__ float half_max(float v) {
     const uint32_t u = __builtin_bit_cast(uint32_t, v);
     const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
     const uint32_t a = r[0], b = r[1];
-    return fmaxf(__builtin_bit_cast(float, a), __builtin_bit_cast(float, b));
+    // plain v_max_f32: fmaxf would first canonicalise both swap results
+    // (two v_max_f32 x, x, x), and neither can be a NaN here
+    float m;
+    asm("v_max_f32 %0, %1, %2" : "=v"(m) : "v"(a), "v"(b));
+    return m;
 }
 __device__ __forceinline__ float half_sum(float v) {
     const uint32_t u = __builtin_bit_cast(uint32_t, v);
@@ -114,10 +124,11 @@ __device__ __forceinline__ float half_sum(float v) {
 }
 
 // head_dim 64 is held to 128 registers: two 8-wave blocks per CU
-template <int NW, int DPAD, bool SPLIT>
+// DFULL: head_dim == DPAD, no 16 B column is padding
+template <int NW, int DPAD, bool DFULL, bool SPLIT>
 __global__ __launch_bounds__(NW * WAVE_SIZE)
 __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
-    FlashAttnParams p) {
+    FlashAttnParams p, bool off32) {
     constexpr int NT = NW * WAVE_SIZE;
     constexpr int QBLK = QW * NW;
     // K rows padded by 8 B: row stride DPAD*2+8 gives gcd(stride/4, 32) = 2,
@@ -162,7 +173,7 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const int d0 = ks * 16 + hi * 8;
-            if (p.Dh == DPAD || d0 + 8 <= p.Dh)
+            if (DFULL || d0 + 8 <= p.Dh)
                 qf[ks] = *reinterpret_cast<const short8*>(qp + d0);
             else
                 qf[ks] = short8{0, 0, 0, 0, 0, 0, 0, 0};
@@ -188,49 +199,101 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
 
     // ---- staging: thread (t-row, 16 B column) moves one b128 piece of K and
     // one of V per pass. cur_chunk/cur_tin locate the first token of the tile
-    // being loaded; tiles advance monotonically. ----
+    // being loaded and kcur/vcur point at it; all four are wave-uniform and
+    // advance monotonically, one tile at a time. ----
     int cur_chunk = 0, cur_tin = 0;
+    const char* kcur = reinterpret_cast<const char*>(kbase);
+    const char* vcur = reinterpret_cast<const char*>(vbase);
     uint4 kreg[NLD], vreg[NLD];
     // piece i of this thread: linear index tid + i*NT over [KVB][KCOLS]. Where
     // a pass covers whole rows the passes differ by a constant row step, which
     // keeps every LDS write address one base plus an immediate.
+    constexpr bool ROWPASS = NT % KCOLS == 0;
     auto stage_row = [&](int i) {
-        if constexpr (NT % KCOLS == 0)
+        if constexpr (ROWPASS)
             return tid / KCOLS + i * (NT / KCOLS);
         else
             return (tid + i * NT) / KCOLS;
     };
     auto stage_col = [&](int i) {
-        if constexpr (NT % KCOLS == 0)
+        if constexpr (ROWPASS)
             return tid % KCOLS;
         else
             return (tid + i * NT) % KCOLS;
     };
-    auto stage_load = [&]<bool MASKED>(int t0) {
+    auto stage_d_ok = [&](int i) { return DFULL || stage_col(i) * 8 + 8 <= p.Dh; };
+    // Byte offset of this thread's first piece from the tile's first token,
+    // fixed for the whole kernel (32-bit: the host passes off32 only when a
+    // tile's span fits); the later pieces add the uniform k_pass/v_pass. Only
+    // whole-row passes (DPAD 64 and 128) have that form: the others would
+    // hold NLD lane offsets per tensor, which DPAD 160 has no registers for.
+    const uint32_t koff = (uint32_t)stage_row(0) * ((uint32_t)p.k_sl * 2) + stage_col(0) * 16;
+    const uint32_t voff = (uint32_t)stage_row(0) * ((uint32_t)p.v_sl * 2) + stage_col(0) * 16;
+    const int k_pass = (NT / KCOLS) * (int)p.k_sl * 2;
+    const int v_pass = (NT / KCOLS) * (int)p.v_sl * 2;
+    // raw buffer descriptor at the (uniform) tile cursor: the load is base in
+    // SGPRs + 32-bit lane offset + scalar pass offset, no 64-bit lane
+    // arithmetic. No range to check against: off32 bounds every offset.
+    auto tile_rsrc = [](const char* cur) {
+        return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(cur), 0, 0xFFFFFFFFu,
+                                                 0x00020000);
+    };
+    // `full`: every token of the tile is below Lkv (all tiles but the tail)
+    auto stage_load = [&](int t0, bool full) {
+        if (ROWPASS && full && off32 && cur_tin + KVB <= LC) {
+            // The tile lies inside one chunk: uniform cursor + fixed lane
+            // offset, and registers about to be overwritten are not zeroed.
+            const auto krs = tile_rsrc(kcur);
+            const auto vrs = tile_rsrc(vcur);
 #pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            const int t_local = stage_row(i);
-            const int d8 = stage_col(i);
-            int tin = cur_tin + t_local;
-            int ch = cur_chunk;
-            while (tin >= LC) {
-                tin -= LC;
-                ++ch;
+            for (int i = 0; i < NLD; ++i) {
+                if constexpr (!DFULL) {
+                    kreg[i] = uint4{0, 0, 0, 0};
+                    vreg[i] = uint4{0, 0, 0, 0};
+                }
+                if (stage_d_ok(i)) {
+                    kreg[i] = __builtin_bit_cast(
+                        uint4, __builtin_amdgcn_raw_buffer_load_b128(
+                                   krs, (int)koff, i * k_pass, 0));
+                    vreg[i] = __builtin_bit_cast(
+                        uint4, __builtin_amdgcn_raw_buffer_load_b128(
+                                   vrs, (int)voff, i * v_pass, 0));
+                }
             }
-            kreg[i] = uint4{0, 0, 0, 0};
-            vreg[i] = uint4{0, 0, 0, 0};
-            const bool d_ok = (p.Dh == DPAD) || (d8 * 8 + 8 <= p.Dh);
-            if (d_ok && (!MASKED || t0 + t_local < Lkv)) {
-                kreg[i] = *reinterpret_cast<const uint4*>(
-                    kbase + ch * p.k_sc + tin * p.k_sl + d8 * 8);
-                vreg[i] = *reinterpret_cast<const uint4*>(
-                    vbase + ch * p.v_sc + tin * p.v_sl + d8 * 8);
+        } else {
+            // A tile that straddles chunks (many of them when LC < KVB), the
+            // tail, or a tensor too large for 32-bit offsets: every row
+            // resolves its own chunk from the cursor.
+#pragma unroll
+            for (int i = 0; i < NLD; ++i) {
+                const int t_local = stage_row(i);
+                const int d8 = stage_col(i);
+                int tin = cur_tin + t_local;
+                int ch = cur_chunk;
+                while (tin >= LC) {
+                    tin -= LC;
+                    ++ch;
+                }
+                kreg[i] = uint4{0, 0, 0, 0};
+                vreg[i] = uint4{0, 0, 0, 0};
+                if (stage_d_ok(i) && t0 + t_local < Lkv) {
+                    kreg[i] = *reinterpret_cast<const uint4*>(
+                        kbase + ch * p.k_sc + tin * p.k_sl + d8 * 8);
+                    vreg[i] = *reinterpret_cast<const uint4*>(
+                        vbase + ch * p.v_sc + tin * p.v_sl + d8 * 8);
+                }
             }
         }
         cur_tin += KVB;
-        while (cur_tin >= LC) {
-            cur_tin -= LC;
-            ++cur_chunk;
+        kcur += KVB * p.k_sl * 2;
+        vcur += KVB * p.v_sl * 2;
+        if (cur_tin >= LC) {  // chunk crossing: re-seat the cursor
+            do {
+                cur_tin -= LC;
+                ++cur_chunk;
+            } while (cur_tin >= LC);
+            kcur = reinterpret_cast<const char*>(kbase + cur_chunk * p.k_sc + cur_tin * p.k_sl);
+            vcur = reinterpret_cast<const char*>(vbase + cur_chunk * p.v_sc + cur_tin * p.v_sl);
         }
     };
     auto stage_write = [&]() {
@@ -371,10 +434,7 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
     const int n_full = Lkv / KVB;
     const int rem = Lkv % KVB;
     if (Lkv > 0) {
-        if (n_full > 0)
-            stage_load.template operator()<false>(0);
-        else
-            stage_load.template operator()<true>(0);
+        stage_load(0, n_full > 0);
         stage_write();
         lds_barrier();
     }
@@ -385,10 +445,7 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
         const int t0 = tile * KVB;
         const bool next_full = tile + 1 < n_full;
         auto load_next = [&]() {
-            if (next_full)
-                stage_load.template operator()<false>(t0 + KVB);
-            else if (rem)
-                stage_load.template operator()<true>(t0 + KVB);
+            if (next_full || rem) stage_load(t0 + KVB, next_full);
         };
         if (SPLIT) load_next();
         compute.template operator()<KVB / 32, false>(t0);
@@ -429,7 +486,7 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
             const auto ry = __builtin_amdgcn_permlane32_swap(ow[2 * g + 1], ow[2 * g + 3],
                                                              false, false);
             const int d0 = dt * 32 + 8 * (g + hi);
-            if (qvalid && (p.Dh == DPAD || d0 + 8 <= p.Dh))
+            if (qvalid && (DFULL || d0 + 8 <= p.Dh))
                 *reinterpret_cast<uint4*>(op + d0) = uint4{rx[0], ry[0], rx[1], ry[1]};
         }
     }
@@ -443,7 +500,15 @@ static void launch_dpad(const FlashAttnParams& p, hipStream_t stream) {
     const int qblk = QW * NW;
     dim3 grid((unsigned)((p.Lq + qblk - 1) / qblk), (unsigned)(p.B * p.H));
     dim3 block(NW * WAVE_SIZE);
-    flash_attn_kernel<NW, DPAD, SPLIT_STAGE><<<grid, block, 0, stream>>>(p);
+    // the in-chunk staging path adds a 32-bit lane offset (a tile's rows and
+    // one row's columns) to the tile cursor; larger token strides stay on the
+    // general 64-bit path
+    const int64_t sl = p.k_sl > p.v_sl ? p.k_sl : p.v_sl;
+    const bool off32 = sl >= 0 && sl * 2 * KVB + DPAD * 2 <= (int64_t)INT32_MAX;
+    if (p.Dh == DPAD)
+        flash_attn_kernel<NW, DPAD, true, SPLIT_STAGE><<<grid, block, 0, stream>>>(p, off32);
+    else
+        flash_attn_kernel<NW, DPAD, false, SPLIT_STAGE><<<grid, block, 0, stream>>>(p, off32);
 }
 
 void launch_flash_attention_d64(const FlashAttnParams& p, hipStream_t stream) {
