@@ -42,6 +42,11 @@
 //   registers before the current tile's compute and written to LDS after the
 //   barrier that ends it; the barriers are raw s_barrier + lgkmcnt-only
 //   waits, so the loads stay in flight across them.
+// * LSE / split-KV mode (template flag; the plain instantiations are
+//   untouched by it): grid.z blocks share a Q block, each over a tile-aligned
+//   slice of the KV range, and write a normalised fp32 partial plus the
+//   slice's log-sum-exp; merge_attn_kernel combines them. Fills the GPU when
+//   Lq is short against Lkv (profiles/attention_splitkv_notes.md).
 //
 // Fragment maps (verified on MI355X by tests/test_ops_gpu.py probes):
 //   16x16x32: A[row=l&15][k=(l>>4)*8+j]  B[k][col=l&15]  D[row=(l>>4)*4+r][col=l&15]
@@ -53,6 +58,9 @@
 
 #include "common.h"
 #include "kernels.h"
+
+#include <algorithm>
+#include <type_traits>
 
 namespace {
 
@@ -125,10 +133,14 @@ __device__ __forceinline__ float half_sum(float v) {
 
 // head_dim 64 is held to 128 registers: two 8-wave blocks per CU
 // DFULL: head_dim == DPAD, no 16 B column is padding
-template <int NW, int DPAD, bool DFULL, bool SPLIT>
+// LSE: the block also emits the softmax log-sum-exp of its rows, and
+// blockIdx.z selects one of gridDim.z tile-aligned slices of the KV range
+// (split-KV): with p.o_part set it writes its normalised partial output as
+// fp32 for merge_attn_kernel, otherwise (one split) bf16 O as the plain mode.
+template <int NW, int DPAD, bool DFULL, bool SPLIT, bool LSE>
 __global__ __launch_bounds__(NW * WAVE_SIZE)
 __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
-    FlashAttnParams p, bool off32) {
+    std::conditional_t<LSE, FlashAttnLseParams, FlashAttnParams> p, bool off32) {
     constexpr int NT = NW * WAVE_SIZE;
     constexpr int QBLK = QW * NW;
     // K rows padded by 8 B: row stride DPAD*2+8 gives gcd(stride/4, 32) = 2,
@@ -204,6 +216,24 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
     int cur_chunk = 0, cur_tin = 0;
     const char* kcur = reinterpret_cast<const char*>(kbase);
     const char* vcur = reinterpret_cast<const char*>(vbase);
+    // Split s of S owns tiles [s*T/S, (s+1)*T/S) of the T = ceil(Lkv/KVB)
+    // tiles: tile-aligned, non-empty for S <= T (host-clamped), and only the
+    // last split reaches the peeled tail. The cursor is seated at the split's
+    // first token, which may lie mid-chunk: the one division of the kernel.
+    int tile_lo = 0, tile_hi = 0;
+    if constexpr (LSE) {
+        const int n_tiles = (Lkv + KVB - 1) / KVB;
+        const int n_splits = (int)gridDim.z, split = (int)blockIdx.z;
+        tile_lo = (int)((int64_t)split * n_tiles / n_splits);
+        tile_hi = (int)((int64_t)(split + 1) * n_tiles / n_splits);
+        if (tile_lo > 0) {
+            const int tok = tile_lo * KVB;
+            cur_chunk = tok / LC;
+            cur_tin = tok - cur_chunk * LC;
+            kcur = reinterpret_cast<const char*>(kbase + cur_chunk * p.k_sc + cur_tin * p.k_sl);
+            vcur = reinterpret_cast<const char*>(vbase + cur_chunk * p.v_sc + cur_tin * p.v_sl);
+        }
+    }
     uint4 kreg[NLD], vreg[NLD];
     // piece i of this thread: linear index tid + i*NT over [KVB][KCOLS]. Where
     // a pass covers whole rows the passes differ by a constant row step, which
@@ -430,18 +460,20 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
         }
     };
 
-    // ---- tile loop: mask-free full tiles, then one peeled tail ----
-    const int n_full = Lkv / KVB;
-    const int rem = Lkv % KVB;
+    // ---- tile loop: mask-free full tiles, then one peeled tail (in LSE mode
+    // over this split's tiles; the tail belongs to the last split) ----
+    const int tile0 = LSE ? tile_lo : 0;
+    const int n_full = LSE ? min(tile_hi, Lkv / KVB) : Lkv / KVB;
+    const int rem = LSE && tile_hi * KVB <= Lkv ? 0 : Lkv % KVB;
     if (Lkv > 0) {
-        stage_load(0, n_full > 0);
+        stage_load(tile0 * KVB, tile0 < n_full);
         stage_write();
         lds_barrier();
     }
     // Q has landed: without this the compiler cannot count the conditional
     // loads behind the Q loads and drains the prefetch at the first QK^T
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only
-    for (int tile = 0; tile < n_full; ++tile) {
+    for (int tile = tile0; tile < n_full; ++tile) {
         const int t0 = tile * KVB;
         const bool next_full = tile + 1 < n_full;
         auto load_next = [&]() {
@@ -466,6 +498,34 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
     // 4hi ..); swapping groups g and g+1 between the halves (guide T21)
     // leaves each lane 8 consecutive d: one 16 B store instead of 8 shorts.
     const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
+    if constexpr (LSE) {
+        // ln sum exp(scale * s) = ln2 * (msc + log2 l): msc is the (possibly
+        // deferred) exp2-domain offset l_run was accumulated against. Both
+        // halves hold the row's value; the lower one stores it.
+        const float lse = l_run > 0.f
+                              ? 0.69314718055994530942f * (msc + __builtin_amdgcn_logf(l_run))
+                              : -__builtin_inff();
+        const int64_t sb = (int64_t)blockIdx.z * p.B + b;
+        if (qvalid && hi == 0) p.lse[(sb * p.H + h) * p.Lq + qrow] = lse;
+        if (p.o_part != nullptr) {
+            // fp32 partial [S, B, Lq, H, Dh]: register group g of a lane is 4
+            // consecutive d (dt*32 + 8g + 4hi ..), one 16 B store each
+            float* op32 = p.o_part + (sb * p.Lq + (qvalid ? qrow : 0)) * (p.H * p.Dh) +
+                          (int64_t)h * p.Dh;
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int d0 = dt * 32 + 8 * g + 4 * hi;
+                    if (qvalid && (DFULL || d0 + 4 <= p.Dh))
+                        *reinterpret_cast<float4*>(op32 + d0) =
+                            float4{ot[dt][4 * g] * inv, ot[dt][4 * g + 1] * inv,
+                                   ot[dt][4 * g + 2] * inv, ot[dt][4 * g + 3] * inv};
+                }
+            }
+            return;
+        }
+    }
     uint16_t* op = p.o + ((int64_t)b * p.Lq + (qvalid ? qrow : 0)) * (p.H * p.Dh) +
                    (int64_t)h * p.Dh;
 #pragma unroll
@@ -494,21 +554,117 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
 
 }  // namespace
 
+namespace {
+
+// ---- merge of split-KV partials --------------------------------------------
+// One thread per (row, 8 d): S x two 16 B fp32 loads, one 16 B bf16 store (or
+// two fp32). Plain HBM-bound streaming; the S weights of a row are re-derived
+// by each of its Dh/8 threads from the (cached) lse parts. Fixed summation
+// order s = 0..S-1, no atomics.
+template <bool OUT_BF16>
+__global__ __launch_bounds__(256) void merge_attn_kernel(MergeAttnParams p) {
+    const int dcols = p.Dh / 8;
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t rows = (int64_t)p.B * p.Lq * p.H;  // (b, q, h), the O row order
+    if (idx >= rows * dcols) return;
+    const int64_t row = idx / dcols;
+    const int dc = (int)(idx - row * dcols);
+    const int h = (int)(row % p.H);
+    const int64_t bq = row / p.H;
+    const int64_t qi = bq % p.Lq;
+    const int64_t b = bq / p.Lq;
+    const int64_t lse_row = (b * p.H + h) * p.Lq + qi;
+    const int64_t lse_ss = (int64_t)p.B * p.H * p.Lq;
+    const int64_t o_ss = rows * p.Dh;
+
+    float m = -__builtin_inff();
+    for (int s = 0; s < p.S; ++s) m = fmaxf(m, p.lse_parts[s * lse_ss + lse_row]);
+    float acc[8] = {};
+    float wsum = 0.f;
+    if (m > -__builtin_inff()) {  // else every part is empty: zeros, lse = -inf
+        const float* src = p.o_parts + row * p.Dh + dc * 8;
+        for (int s = 0; s < p.S; ++s) {
+            const float w = expf(p.lse_parts[s * lse_ss + lse_row] - m);  // exp(-inf) = 0
+            const float4 a = *reinterpret_cast<const float4*>(src + s * o_ss);
+            const float4 c = *reinterpret_cast<const float4*>(src + s * o_ss + 4);
+            if (w > 0.f) {  // an empty part may hold anything
+                wsum += w;
+                acc[0] += w * a.x, acc[1] += w * a.y, acc[2] += w * a.z, acc[3] += w * a.w;
+                acc[4] += w * c.x, acc[5] += w * c.y, acc[6] += w * c.z, acc[7] += w * c.w;
+            }
+        }
+        const float inv = 1.f / wsum;  // wsum >= 1: the max part has weight 1
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] *= inv;
+    }
+    if (OUT_BF16) {
+        uint32_t w[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint32_t e0 = __builtin_bit_cast(uint16_t, __float2bfloat16(acc[2 * j]));
+            const uint32_t e1 = __builtin_bit_cast(uint16_t, __float2bfloat16(acc[2 * j + 1]));
+            w[j] = e0 | (e1 << 16);
+        }
+        *reinterpret_cast<uint4*>(static_cast<uint16_t*>(p.out) + row * p.Dh + dc * 8) =
+            uint4{w[0], w[1], w[2], w[3]};
+    } else {
+        float* dst = static_cast<float*>(p.out) + row * p.Dh + dc * 8;
+        *reinterpret_cast<float4*>(dst) = float4{acc[0], acc[1], acc[2], acc[3]};
+        *reinterpret_cast<float4*>(dst + 4) = float4{acc[4], acc[5], acc[6], acc[7]};
+    }
+    if (dc == 0 && p.lse != nullptr)
+        p.lse[lse_row] = wsum > 0.f ? m + logf(wsum) : -__builtin_inff();
+}
+
+}  // namespace
+
+void launch_merge_attention(const MergeAttnParams& p, hipStream_t stream) {
+    const int64_t total = (int64_t)p.B * p.Lq * p.H * (p.Dh / 8);
+    if (total == 0) return;
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (p.out_bf16)
+        merge_attn_kernel<true><<<grid, 256, 0, stream>>>(p);
+    else
+        merge_attn_kernel<false><<<grid, 256, 0, stream>>>(p);
+}
+
+namespace {
+
+// the in-chunk staging path adds a 32-bit lane offset (a tile's rows and one
+// row's columns) to the tile cursor; larger token strides stay on the general
+// 64-bit path
+template <int DPAD>
+bool fits_off32(const FlashAttnParams& p) {
+    const int64_t sl = p.k_sl > p.v_sl ? p.k_sl : p.v_sl;
+    return sl >= 0 && sl * 2 * KVB + DPAD * 2 <= (int64_t)INT32_MAX;
+}
+
+template <int DPAD>
+void launch_dpad_lse(const FlashAttnLseParams& p, int splits, hipStream_t stream) {
+    constexpr int NW = 8;
+    const int qblk = QW * NW;
+    dim3 grid((unsigned)((p.Lq + qblk - 1) / qblk), (unsigned)(p.B * p.H), (unsigned)splits);
+    dim3 block(NW * WAVE_SIZE);
+    const bool off32 = fits_off32<DPAD>(p);
+    if (p.Dh == DPAD)
+        flash_attn_kernel<NW, DPAD, true, SPLIT_STAGE, true><<<grid, block, 0, stream>>>(p, off32);
+    else
+        flash_attn_kernel<NW, DPAD, false, SPLIT_STAGE, true><<<grid, block, 0, stream>>>(p, off32);
+}
+
+}  // namespace
+
 template <int DPAD>
 static void launch_dpad(const FlashAttnParams& p, hipStream_t stream) {
     constexpr int NW = 8;
     const int qblk = QW * NW;
     dim3 grid((unsigned)((p.Lq + qblk - 1) / qblk), (unsigned)(p.B * p.H));
     dim3 block(NW * WAVE_SIZE);
-    // the in-chunk staging path adds a 32-bit lane offset (a tile's rows and
-    // one row's columns) to the tile cursor; larger token strides stay on the
-    // general 64-bit path
-    const int64_t sl = p.k_sl > p.v_sl ? p.k_sl : p.v_sl;
-    const bool off32 = sl >= 0 && sl * 2 * KVB + DPAD * 2 <= (int64_t)INT32_MAX;
+    const bool off32 = fits_off32<DPAD>(p);
     if (p.Dh == DPAD)
-        flash_attn_kernel<NW, DPAD, true, SPLIT_STAGE><<<grid, block, 0, stream>>>(p, off32);
+        flash_attn_kernel<NW, DPAD, true, SPLIT_STAGE, false><<<grid, block, 0, stream>>>(p, off32);
     else
-        flash_attn_kernel<NW, DPAD, false, SPLIT_STAGE><<<grid, block, 0, stream>>>(p, off32);
+        flash_attn_kernel<NW, DPAD, false, SPLIT_STAGE, false><<<grid, block, 0, stream>>>(p, off32);
 }
 
 void launch_flash_attention_d64(const FlashAttnParams& p, hipStream_t stream) {
@@ -523,6 +679,23 @@ void launch_flash_attention_d64(const FlashAttnParams& p, hipStream_t stream) {
         launch_dpad<128>(p, stream);
     else
         launch_dpad<160>(p, stream);
+}
+
+int flash_attention_num_splits(int64_t lkv, int splits) {
+    const int64_t tiles = (lkv + KVB - 1) / KVB;
+    return (int)std::max<int64_t>(1, std::min<int64_t>(splits, tiles));
+}
+
+void launch_flash_attention_lse(const FlashAttnLseParams& p, int splits, hipStream_t stream) {
+    splits = flash_attention_num_splits(p.NC * p.LC, splits);
+    if (p.Dh <= 64)
+        launch_dpad_lse<64>(p, splits, stream);
+    else if (p.Dh <= 96)
+        launch_dpad_lse<96>(p, splits, stream);
+    else if (p.Dh <= 128)
+        launch_dpad_lse<128>(p, splits, stream);
+    else
+        launch_dpad_lse<160>(p, splits, stream);
 }
 
 // ---- fragment-layout probes (tests/test_ops_gpu.py) ------------------------

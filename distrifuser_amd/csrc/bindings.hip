@@ -143,8 +143,9 @@ at::Tensor cfg_affine_step(const at::Tensor& noise, const at::Tensor& x, double 
     return out;
 }
 
-at::Tensor flash_attention(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v) {
-    // q: [B,H,Lq,64]; k/v: [B,H,Lkv,64] or [B,H,NC,LC,64] (stale-KV chunks)
+// q: [B,H,Lq,D]; k/v: [B,H,Lkv,D] or [B,H,NC,LC,D] (stale-KV chunks): checks
+// and everything of FlashAttnParams but the output pointer
+FlashAttnParams flash_params(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v) {
     TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16, "flash_attention: bf16 only");
     const int Dh = (int)q.size(-1);
     TORCH_CHECK(q.dim() == 4 && Dh % 8 == 0 && Dh <= 160,
@@ -195,11 +196,112 @@ at::Tensor flash_attention(const at::Tensor& q, const at::Tensor& k, const at::T
     set_kv(v, p.v, p.v_sb, p.v_sh, p.v_sc, p.v_sl, nc2, lc2);
     TORCH_CHECK(nc2 == p.NC && lc2 == p.LC, "k/v shape mismatch");
     TORCH_CHECK(p.q_sl % 8 == 0 && p.q_sb % 8 == 0 && p.q_sh % 8 == 0);
+    return p;
+}
 
-    auto o = at::empty({(long)B, (long)Lq, (long)H, (long)Dh}, q.options());
+at::Tensor flash_attention(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v) {
+    FlashAttnParams p = flash_params(q, k, v);
+    auto o = at::empty({(long)p.B, (long)p.Lq, (long)p.H, (long)p.Dh}, q.options());
     p.o = reinterpret_cast<uint16_t*>(o.data_ptr());
     launch_flash_attention_d64(p, cur_stream());
     return o.permute({0, 2, 1, 3});  // logical [B,H,Lq,64]
+}
+
+// Split-KV partials into caller-owned buffers: o_part fp32 [S,B,Lq,H,D] and
+// lse_part fp32 [S,B,H,Lq], S = the number of splits actually used (kv_splits
+// clamped to the number of 128-token tiles), which is returned.
+int64_t flash_attention_partial(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                                int64_t kv_splits, at::Tensor o_part, at::Tensor lse_part) {
+    TORCH_CHECK(kv_splits >= 1, "kv_splits must be >= 1");
+    FlashAttnLseParams p{flash_params(q, k, v)};
+    const int S = flash_attention_num_splits(p.NC * p.LC, (int)std::min<int64_t>(kv_splits, 1 << 16));
+    TORCH_CHECK(o_part.is_cuda() && o_part.scalar_type() == at::kFloat && o_part.is_contiguous() &&
+                    o_part.sizes() == (at::IntArrayRef{(long)S, (long)p.B, (long)p.Lq, (long)p.H,
+                                                       (long)p.Dh}),
+                "o_part must be contiguous fp32 [S,B,Lq,H,D] with S = ", S);
+    TORCH_CHECK(lse_part.is_cuda() && lse_part.scalar_type() == at::kFloat &&
+                    lse_part.is_contiguous() &&
+                    lse_part.sizes() == (at::IntArrayRef{(long)S, (long)p.B, (long)p.H, (long)p.Lq}),
+                "lse_part must be contiguous fp32 [S,B,H,Lq] with S = ", S);
+    p.o_part = o_part.data_ptr<float>();
+    p.lse = lse_part.data_ptr<float>();
+    launch_flash_attention_lse(p, S, cur_stream());
+    return S;
+}
+
+at::Tensor merge_attention_into(const at::Tensor& o_parts, const at::Tensor& lse_parts,
+                                bool out_bf16, const c10::optional<at::Tensor>& lse_out) {
+    TORCH_CHECK(o_parts.is_cuda() && o_parts.dim() == 5 && o_parts.scalar_type() == at::kFloat &&
+                    o_parts.is_contiguous(),
+                "merge_attention: o_parts must be contiguous fp32 [S,B,Lq,H,D]");
+    MergeAttnParams m{};
+    m.S = (int)o_parts.size(0);
+    m.B = (int)o_parts.size(1);
+    m.Lq = o_parts.size(2);
+    m.H = (int)o_parts.size(3);
+    m.Dh = (int)o_parts.size(4);
+    TORCH_CHECK(m.S >= 1 && m.Dh % 8 == 0, "merge_attention: S >= 1 and head_dim % 8 == 0");
+    TORCH_CHECK(lse_parts.is_cuda() && lse_parts.scalar_type() == at::kFloat &&
+                    lse_parts.is_contiguous() &&
+                    lse_parts.sizes() ==
+                        (at::IntArrayRef{(long)m.S, (long)m.B, (long)m.H, (long)m.Lq}),
+                "merge_attention: lse_parts must be contiguous fp32 [S,B,H,Lq]");
+    auto out = at::empty({(long)m.B, (long)m.Lq, (long)m.H, (long)m.Dh},
+                         o_parts.options().dtype(out_bf16 ? at::kBFloat16 : at::kFloat));
+    m.o_parts = o_parts.data_ptr<float>();
+    m.lse_parts = lse_parts.data_ptr<float>();
+    m.out = out.data_ptr();
+    m.out_bf16 = out_bf16;
+    if (lse_out.has_value()) m.lse = lse_out->data_ptr<float>();
+    launch_merge_attention(m, cur_stream());
+    return out;
+}
+
+// parts stacked on dim 0 -> (out [B,Lq,H,D] bf16 or fp32, lse [B,H,Lq])
+std::vector<at::Tensor> merge_attention(const at::Tensor& o_parts, const at::Tensor& lse_parts,
+                                        bool out_bf16) {
+    TORCH_CHECK(lse_parts.dim() == 4, "merge_attention: lse_parts must be [S,B,H,Lq]");
+    auto lse = at::empty({lse_parts.size(1), lse_parts.size(2), lse_parts.size(3)},
+                         lse_parts.options());
+    auto out = merge_attention_into(o_parts, lse_parts, out_bf16, lse);
+    return {out, lse};
+}
+
+// flash_attention with split-KV and an optional log-sum-exp output. Returns
+// {out [B,H,Lq,D] (a view of [B,Lq,H,D])} or {out, lse [B,H,Lq] fp32}.
+// kv_splits > 1 (after clamping to the tile count) runs the partial kernel
+// over grid.z = S and then the merge kernel, on the current stream; the fp32
+// workspace comes from the caching allocator (safe under graph capture).
+std::vector<at::Tensor> flash_attention_ext(const at::Tensor& q, const at::Tensor& k,
+                                            const at::Tensor& v, int64_t kv_splits,
+                                            bool return_lse) {
+    TORCH_CHECK(kv_splits >= 1, "kv_splits must be >= 1");
+    FlashAttnLseParams p{flash_params(q, k, v)};
+    const int S = flash_attention_num_splits(p.NC * p.LC, (int)std::min<int64_t>(kv_splits, 1 << 16));
+    const auto f32 = q.options().dtype(at::kFloat);
+    const long B = p.B, H = p.H, Lq = p.Lq, Dh = p.Dh;
+    if (S == 1) {
+        auto o = at::empty({B, Lq, H, Dh}, q.options());
+        p.o = reinterpret_cast<uint16_t*>(o.data_ptr());
+        if (!return_lse) {
+            launch_flash_attention_d64(p, cur_stream());
+            return {o.permute({0, 2, 1, 3})};
+        }
+        auto lse = at::empty({B, H, Lq}, f32);
+        p.lse = lse.data_ptr<float>();
+        launch_flash_attention_lse(p, 1, cur_stream());
+        return {o.permute({0, 2, 1, 3}), lse};
+    }
+    auto o_part = at::empty({(long)S, B, Lq, H, Dh}, f32);
+    auto lse_part = at::empty({(long)S, B, H, Lq}, f32);
+    p.o_part = o_part.data_ptr<float>();
+    p.lse = lse_part.data_ptr<float>();
+    launch_flash_attention_lse(p, S, cur_stream());
+    if (!return_lse)
+        return {merge_attention_into(o_part, lse_part, true, c10::nullopt).permute({0, 2, 1, 3})};
+    auto lse = at::empty({B, H, Lq}, f32);
+    auto o = merge_attention_into(o_part, lse_part, true, lse);
+    return {o.permute({0, 2, 1, 3}), lse};
 }
 
 at::Tensor conv3x3(const at::Tensor& x, const at::Tensor& wp,
@@ -388,6 +490,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "merge stale peer GN moments with fresh local ones (one launch)");
     m.def("cfg_affine_step", &cfg_affine_step, "fused CFG combine + affine scheduler update");
     m.def("flash_attention", &flash_attention, "bf16 d64 flash attention (chunked stale KV)");
+    m.def("flash_attention_ext", &flash_attention_ext,
+          "flash attention with split-KV and optional log-sum-exp -> [out] or [out, lse]",
+          pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"),
+          pybind11::arg("kv_splits") = 1, pybind11::arg("return_lse") = false);
+    m.def("flash_attention_partial", &flash_attention_partial,
+          "split-KV partials into caller buffers (o_part fp32 [S,B,Lq,H,D], lse_part [S,B,H,Lq])");
+    m.def("merge_attention", &merge_attention,
+          "merge fp32 attention partials by their log-sum-exp -> [out, lse]",
+          pybind11::arg("o_parts"), pybind11::arg("lse_parts"), pybind11::arg("out_bf16") = true);
     m.def("cfg_dpm_step", &cfg_dpm_step, "fused CFG + DPM-Solver++(2M) update -> (prev, x0)");
     m.def("layer_norm", &layer_norm, "bf16 fused LayerNorm");
     m.def("add_layer_norm", &add_layer_norm, "bf16 fused residual-add + LayerNorm -> (sum, y)");

@@ -111,3 +111,33 @@ struct FlashAttnParams {
     float scale;  // 1/sqrt(64)
 };
 void launch_flash_attention_d64(const FlashAttnParams& p, hipStream_t stream);
+
+// LSE / split-KV mode of the same kernel. lse: fp32 [S, B, H, Lq], the natural
+// log of each row's sum of exp(scale * q.k) over the split's KV slice (-inf
+// for an empty slice). o_part == null (S == 1 only): bf16 O goes to `o` as in
+// the plain mode. o_part != null: split s writes its normalised partial
+// output as fp32 into o_part [S, B, Lq, H, Dh]; `o` is not touched.
+struct FlashAttnLseParams : FlashAttnParams {
+    float* lse;
+    float* o_part;
+};
+// S the launcher uses for a request of `splits`: clamped to [1, ceil(Lkv/128)]
+// (splits are tile-aligned and never empty).
+int flash_attention_num_splits(int64_t lkv, int splits);
+void launch_flash_attention_lse(const FlashAttnLseParams& p, int splits, hipStream_t stream);
+
+// ---- merge of attention partials ----------------------------------------------
+// out[b,q,h,:] = sum_s w_s o_parts[s,b,q,h,:] / sum_s w_s, w_s = exp(lse_s - max_s lse_s);
+// lse = max + ln sum_s w_s (optional). A part with lse = -inf has weight 0; all
+// parts -inf gives zeros and lse = -inf. o_parts fp32 [S, B, Lq, H, Dh],
+// lse_parts fp32 [S, B, H, Lq], out [B, Lq, H, Dh] bf16 or fp32, Dh % 8 == 0.
+struct MergeAttnParams {
+    const float* o_parts;
+    const float* lse_parts;
+    void* out;
+    float* lse;  // [B, H, Lq] or null
+    int S, B, H, Dh;
+    int64_t Lq;
+    bool out_bf16;
+};
+void launch_merge_attention(const MergeAttnParams& p, hipStream_t stream);

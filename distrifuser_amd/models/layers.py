@@ -41,10 +41,12 @@ class PlainGroupNorm(nn.GroupNorm):
 
 
 class PlainSelfAttention(nn.Module):
-    def __init__(self, query_dim: int, heads: int, dim_head: int, out_bias: bool = True):
+    def __init__(self, query_dim: int, heads: int, dim_head: int, out_bias: bool = True,
+                 config=None):
         super().__init__()
         inner = heads * dim_head
         self.heads, self.dim_head = heads, dim_head
+        self.config = config  # DistriConfig: the split-KV knob (None: no splitting)
         self.to_q = nn.Linear(query_dim, inner, bias=False)
         self.to_kv = nn.Linear(query_dim, 2 * inner, bias=False)
         self.to_out = nn.Linear(inner, query_dim, bias=out_bias)
@@ -56,7 +58,10 @@ class PlainSelfAttention(nn.Module):
         k, v = self.to_kv(x).split(inner, dim=-1)
         k = k.view(b, l, self.heads, self.dim_head).transpose(1, 2)
         v = v.view(b, l, self.heads, self.dim_head).transpose(1, 2)
-        out = ops.flash_attention(q, k, v).transpose(1, 2).reshape(b, l, inner)
+        splits = 1
+        if self.config is not None:
+            splits = self.config.attn_splits(b, self.heads, l, l, self.dim_head)
+        out = ops.flash_attention(q, k, v, kv_splits=splits).transpose(1, 2).reshape(b, l, inner)
         return self.to_out(out)
 
 
@@ -141,7 +146,7 @@ class LayerFactory:
             return PatchSelfAttention(dim, heads, dim_head, state=self.state)
         if self.parallelism == "tensor" and self.state.config.n_device_per_batch > 1:
             return TPAttention(dim, heads, dim_head, state=self.state)
-        return PlainSelfAttention(dim, heads, dim_head)
+        return PlainSelfAttention(dim, heads, dim_head, config=self.state.config)
 
     def cross_attention(self, dim: int, cross_dim: int, heads: int, dim_head: int) -> nn.Module:
         if self.parallelism == "patch":

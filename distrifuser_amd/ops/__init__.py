@@ -10,6 +10,7 @@ Set DFA_FORCE_EAGER=1 to force the eager path on GPU (A/B debugging only).
 from .conv import NativeConv2d, conv3x3_halo, pack_conv3x3_weight
 from .dispatch import (
     add_layer_norm,
+    attention_kv_splits,
     flash_attention,
     flash_attention_chunked,
     geglu,
@@ -19,12 +20,14 @@ from .dispatch import (
     hip_ext,
     hip_ext_available,
     layer_norm,
+    merge_attention,
     vae_attention,
 )
 
 __all__ = [
     "NativeConv2d",
     "add_layer_norm",
+    "attention_kv_splits",
     "layer_norm",
     "conv3x3_halo",
     "flash_attention",
@@ -35,6 +38,7 @@ __all__ = [
     "group_norm_stats",
     "hip_ext",
     "hip_ext_available",
+    "merge_attention",
     "pack_conv3x3_weight",
     "vae_attention",
 ]

@@ -68,27 +68,51 @@ def _flash_ok(q: torch.Tensor, *kv: torch.Tensor) -> bool:
     return True
 
 
-def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+def _check_kv_splits(kv_splits: int) -> int:
+    if isinstance(kv_splits, bool) or not isinstance(kv_splits, int) or kv_splits < 1:
+        raise ValueError(f"kv_splits must be a positive int, got {kv_splits!r}")
+    return kv_splits
+
+
+def flash_attention(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    *,
+    kv_splits: int = 1,
+    return_lse: bool = False,
+):
     """Attention over (possibly strided) full-sequence KV.
 
     q: [B, H, Lq, D]; k, v: [B, H, Lkv, D] (arbitrary stride in the Lkv dim).
+    kv_splits > 1 splits the KV range over that many blocks per Q block
+    (clamped to the number of 128-token tiles) and merges the partials: same
+    result up to fp32 rounding, a fuller grid when Lq is short. return_lse
+    adds the fp32 softmax log-sum-exp [B, H, Lq]: returns (out, lse). The
+    eager path accepts kv_splits and ignores it.
     """
-    if _use_hip(q):
-        if _flash_ok(q, k, v):
+    _check_kv_splits(kv_splits)
+    if _use_hip(q) and _flash_ok(q, k, v):
+        if kv_splits == 1 and not return_lse:
             return hip_ext().flash_attention(q, k, v)
-        # Non-bf16 / odd head-dims ride PyTorch's SDPA (rocm AOTriton path).
-        return eager.flash_attention(q, k, v)
+        res = hip_ext().flash_attention_ext(q, k, v, kv_splits, return_lse)
+        return (res[0], res[1]) if return_lse else res[0]
+    # CPU, or non-bf16 / odd head-dims on GPU (PyTorch's SDPA, rocm AOTriton path)
+    if return_lse:
+        return eager.flash_attention_lse(q, k, v)
     return eager.flash_attention(q, k, v)
 
 
 def flash_attention_chunked(
-    q: torch.Tensor, kv_chunks: torch.Tensor, heads: int, dim_head: int
+    q: torch.Tensor, kv_chunks: torch.Tensor, heads: int, dim_head: int, kv_splits: int = 1
 ) -> torch.Tensor:
     """Displaced-patch attention: q [B, Lq, inner]; kv_chunks is the flat comm
     buffer viewed as [n_peers, B, L_local, 2*inner] (strided — peer rows live
-    in the flat buffer). On GPU the gfx950 kernel walks the chunks in place;
-    the eager path materializes the concatenated KV.
+    in the flat buffer). On GPU the gfx950 kernel walks the chunks in place
+    (kv_splits as in flash_attention; a split may start mid-chunk); the eager
+    path materializes the concatenated KV.
     """
+    _check_kv_splits(kv_splits)
     b, lq, inner = q.shape
     n, _, l, _ = kv_chunks.shape
     if _use_hip(q):
@@ -96,15 +120,112 @@ def flash_attention_chunked(
         k = kv_chunks[..., :inner].unflatten(-1, (heads, dim_head)).permute(1, 3, 0, 2, 4)
         v = kv_chunks[..., inner:].unflatten(-1, (heads, dim_head)).permute(1, 3, 0, 2, 4)
         if _flash_ok(q4, k, v):
-            o = hip_ext().flash_attention(q4, k, v)  # [B,H,Lq,D] (view of B,Lq,H,D)
+            if kv_splits == 1:
+                o = hip_ext().flash_attention(q4, k, v)  # [B,H,Lq,D] (view of B,Lq,H,D)
+            else:
+                o = hip_ext().flash_attention_ext(q4, k, v, kv_splits, False)[0]
             return o.transpose(1, 2).reshape(b, lq, inner)
     full_kv = kv_chunks.permute(1, 0, 2, 3).reshape(b, n * l, 2 * inner)
     k, v = full_kv.split(inner, dim=-1)
     q4 = q.view(b, lq, heads, dim_head).transpose(1, 2)
     k = k.view(b, n * l, heads, dim_head).transpose(1, 2)
     v = v.view(b, n * l, heads, dim_head).transpose(1, 2)
-    out = flash_attention(q4, k.contiguous(), v.contiguous())
+    out = flash_attention(q4, k.contiguous(), v.contiguous(), kv_splits=kv_splits)
     return out.transpose(1, 2).reshape(b, lq, inner)
+
+
+def merge_attention(
+    o_parts: torch.Tensor,
+    lse_parts: torch.Tensor,
+    *,
+    out_dtype: torch.dtype | None = None,
+    return_lse: bool = False,
+):
+    """Merge attention results over disjoint KV slices by their log-sum-exp.
+
+    o_parts: [S, B, Lq, H, D] (each part normalised over its own slice),
+    lse_parts: [S, B, H, Lq]. Returns out [B, Lq, H, D] in out_dtype (default:
+    the parts' dtype), with return_lse also the merged fp32 lse [B, H, Lq].
+    Parts with lse = -inf weigh 0; all -inf gives zeros and lse = -inf. The
+    gfx950 kernel takes contiguous fp32 parts and writes bf16 or fp32;
+    anything else runs the eager reference.
+    """
+    dt = o_parts.dtype if out_dtype is None else out_dtype
+    if (
+        _use_hip(o_parts)
+        and o_parts.dtype == torch.float32
+        and lse_parts.dtype == torch.float32
+        and dt in (torch.bfloat16, torch.float32)
+        and o_parts.dim() == 5
+        and o_parts.shape[-1] % 8 == 0
+        and o_parts.is_contiguous()
+        and lse_parts.is_contiguous()
+    ):
+        out, lse = hip_ext().merge_attention(o_parts, lse_parts, dt == torch.bfloat16)
+    else:
+        out, lse = eager.merge_attention(o_parts, lse_parts, dt)
+    return (out, lse) if return_lse else out
+
+
+# Split-KV policy: a three-constant cost model fitted to the sweep in
+# profiles/attention_splitkv_notes.md (24 timings, six shapes, head_dim 64).
+_KV_TILE = 128  # KV tokens per LDS tile of the kernel; splits are tile-aligned
+_Q_BLOCK = 256  # Q rows per block
+_TILE_US = 2.4  # one 128-token tile of one block alone on its CU (DPAD 64)
+_MERGE_LAUNCH_US = 5.0  # the second launch of a split call
+_MERGE_BYTES_PER_US = 4.0e6  # fp32 partials written once and read once
+_BLOCKS_PER_CU = 2  # resident 8-wave blocks per CU at DPAD 64 (128 VGPRs)
+_MIN_TILES_PER_SPLIT = 2  # one-tile splits measured slower than two-tile ones
+_MAX_KV_SPLITS = 8
+_MIN_GAIN = 0.05  # predicted gain below this stays unsplit
+_DEFAULT_CUS = 256  # MI355X
+
+
+def attention_kv_splits(
+    b: int,
+    heads: int,
+    lq: int,
+    lkv: int,
+    dim_head: int,
+    device=None,
+    *,
+    multi_processor_count: int | None = None,
+) -> int:
+    """How many KV splits the attention kernel should use for this shape.
+
+    Pure shape arithmetic (never synchronises; reads the CU count from the
+    device properties unless multi_processor_count is given). Blocks that
+    share a CU share its throughput, so with blocks = ceil(lq/256) * b * heads
+    and T = ceil(lkv/128) a call costs about
+        ceil(T/S) * ceil(blocks * S / CUs) tile times
+    plus, for S > 1, a second launch and the fp32 partials' round trip through
+    memory. The S in {1, 2, 4, 8}, S <= T // 2, with the least predicted time is returned
+    if it gains at least 5 %, else 1. A grid that already takes every resident
+    block slot (2 per CU) returns 1 outright, and a short KV range
+    (cross-attention, Lkv = 77) has nothing to split. Head dims above 64 return 1: no sweep covers them.
+    """
+    if dim_head > 64 or min(b, heads, lq, lkv) <= 0:
+        return 1
+    cus = multi_processor_count
+    if cus is None:
+        cus = _DEFAULT_CUS
+        if torch.cuda.is_available() and (device is None or torch.device(device).type == "cuda"):
+            cus = torch.cuda.get_device_properties(device).multi_processor_count
+    blocks = -(-lq // _Q_BLOCK) * b * heads
+    tiles = -(-lkv // _KV_TILE)
+    if blocks >= cus * _BLOCKS_PER_CU:
+        return 1  # every resident-block slot is taken: the plain grid fills the GPU
+    part_bytes = 2 * 4 * b * heads * lq * dim_head  # one part: written, then read
+
+    def cost(s: int) -> float:
+        t = _TILE_US * -(-tiles // s) * -(-blocks * s // cus)
+        if s > 1:
+            t += _MERGE_LAUNCH_US + s * part_bytes / _MERGE_BYTES_PER_US
+        return t
+
+    s_max = max(1, min(_MAX_KV_SPLITS, tiles // _MIN_TILES_PER_SPLIT))
+    best = min((s for s in (1, 2, 4, 8) if s <= s_max), key=cost)  # the S values swept
+    return best if cost(best) < (1.0 - _MIN_GAIN) * cost(1) else 1
 
 
 def group_norm_stats(x: torch.Tensor, num_groups: int) -> torch.Tensor:

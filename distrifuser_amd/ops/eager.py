@@ -20,6 +20,47 @@ def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.
     return F.scaled_dot_product_attention(q, k, v, dropout_p=0.0, is_causal=False)
 
 
+def flash_attention_lse(
+    q: torch.Tensor, k: torch.Tensor, v: torch.Tensor
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """fp32 reference of attention with its softmax log-sum-exp.
+
+    Returns (out [B, H, Lq, D] in q.dtype, lse [B, H, Lq] fp32) with
+    lse = ln sum_k exp(q.k / sqrt(d)). An empty KV range gives out = 0 and
+    lse = -inf.
+    """
+    scores = torch.einsum("bhqd,bhkd->bhqk", q.float(), k.float()) * q.shape[-1] ** -0.5
+    lse = torch.logsumexp(scores, dim=-1)
+    probs = torch.exp(scores - lse.unsqueeze(-1))
+    out = torch.einsum("bhqk,bhkd->bhqd", probs, v.float())
+    return out.to(q.dtype), lse
+
+
+def merge_attention(
+    o_parts: torch.Tensor, lse_parts: torch.Tensor, out_dtype: torch.dtype | None = None
+) -> tuple[torch.Tensor, torch.Tensor]:
+    """Merge attention results computed over disjoint KV slices.
+
+    o_parts: [S, B, Lq, H, D] normalised partial outputs; lse_parts:
+    [S, B, H, Lq]. With m = max_s lse_s and w_s = exp(lse_s - m):
+    out = sum_s w_s o_s / sum_s w_s and lse = m + ln sum_s w_s, summed in part
+    order in fp32. A part with lse = -inf has weight 0 whatever it holds; if
+    every part is -inf the output is zeros and lse = -inf (never NaN).
+    Returns (out [B, Lq, H, D], lse [B, H, Lq] fp32).
+    """
+    lse_f = lse_parts.float()
+    m = lse_f.max(dim=0).values
+    empty = torch.isneginf(m)
+    w = torch.exp(lse_f - torch.where(empty, torch.zeros_like(m), m))  # exp(-inf) = 0
+    wsum = w.sum(dim=0)
+    wq = w.permute(0, 1, 3, 2).unsqueeze(-1)  # [S, B, Lq, H, 1]
+    acc = torch.where(wq > 0, wq * o_parts.float(), torch.zeros((), device=w.device)).sum(dim=0)
+    denom = torch.where(empty, torch.ones_like(wsum), wsum).permute(0, 2, 1).unsqueeze(-1)
+    out = acc / denom
+    lse = torch.where(empty, m, m + torch.log(wsum))
+    return out.to(o_parts.dtype if out_dtype is None else out_dtype), lse
+
+
 def group_norm_stats(x: torch.Tensor, num_groups: int) -> torch.Tensor:
     """Per-(sample, group) first/second moments over (group_size, H, W).
 

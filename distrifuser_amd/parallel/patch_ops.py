@@ -381,7 +381,8 @@ class PatchSelfAttention(nn.Module):
         q = q.view(b, lq, self.heads, self.dim_head).transpose(1, 2)
         k = k.view(b, lkv, self.heads, self.dim_head).transpose(1, 2)
         v = v.view(b, lkv, self.heads, self.dim_head).transpose(1, 2)
-        out = ops.flash_attention(q, k, v)
+        splits = self.state.config.attn_splits(b, self.heads, lq, lkv, self.dim_head)
+        out = ops.flash_attention(q, k, v, kv_splits=splits)
         return out.transpose(1, 2).reshape(b, lq, inner)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -428,7 +429,10 @@ class PatchSelfAttention(nn.Module):
         # The buffer view [n, B, L, 2C] IS the full displaced KV (peers are
         # ordered by patch index = full image row order); the kernel walks the
         # peer chunks in place — no torch.cat on the hot path.
-        out = ops.flash_attention_chunked(q, self._buffer_view, self.heads, self.dim_head)
+        splits = cfg.attn_splits(b, self.heads, l, cfg.n_device_per_batch * l, self.dim_head)
+        out = ops.flash_attention_chunked(
+            q, self._buffer_view, self.heads, self.dim_head, kv_splits=splits
+        )
         return self.to_out(out)
 
 

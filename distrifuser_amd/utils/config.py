@@ -32,6 +32,27 @@ VALID_PARALLELISM = ("patch", "tensor", "naive_patch")
 VALID_SPLIT_SCHEMES = ("row", "col", "alternate")
 
 
+class _UnsetInt(int):
+    """An int default that can be told apart from the same value passed in."""
+
+
+_ATTN_KV_SPLITS_UNSET = _UnsetInt(1)
+
+
+def _parse_attn_kv_splits(value) -> int | str:
+    """A positive int or "auto" (ints may arrive as strings from the environment)."""
+    if isinstance(value, str):
+        if value.strip().lower() == "auto":
+            return "auto"
+        try:
+            value = int(value)
+        except ValueError:
+            raise ValueError(f"attn_kv_splits must be a positive int or 'auto', got {value!r}")
+    if isinstance(value, bool) or not isinstance(value, int) or value < 1:
+        raise ValueError(f"attn_kv_splits must be a positive int or 'auto', got {value!r}")
+    return int(value)
+
+
 def is_power_of_2(n: int) -> bool:
     return n >= 1 and (n & (n - 1)) == 0
 
@@ -68,7 +89,14 @@ class DistriConfig:
         verbose: bool = False,
         backend: str | None = None,
         device: str | torch.device | None = None,
+        attn_kv_splits: int | str = _ATTN_KV_SPLITS_UNSET,
     ):
+        # Self-attention split-KV: a positive int, or "auto" for
+        # ops.attention_kv_splits per call site. Left at its default (1), the
+        # DFA_ATTN_KV_SPLITS environment variable takes its place.
+        if attn_kv_splits is _ATTN_KV_SPLITS_UNSET:
+            attn_kv_splits = os.environ.get("DFA_ATTN_KV_SPLITS") or 1
+        self.attn_kv_splits = _parse_attn_kv_splits(attn_kv_splits)
         assert mode in VALID_MODES, f"mode must be one of {VALID_MODES}, got {mode!r}"
         assert parallelism in VALID_PARALLELISM, (
             f"parallelism must be one of {VALID_PARALLELISM}, got {parallelism!r}"
@@ -188,6 +216,15 @@ class DistriConfig:
         return rank % self.n_device_per_batch
 
     # -- conveniences ------------------------------------------------------
+
+    def attn_splits(self, b: int, heads: int, lq: int, lkv: int, dim_head: int) -> int:
+        """kv_splits for one self-attention call of this shape (the knob, or
+        the shape heuristic under "auto")."""
+        if self.attn_kv_splits == "auto":
+            from ..ops import attention_kv_splits
+
+            return attention_kv_splits(b, heads, lq, lkv, dim_head, self.device)
+        return self.attn_kv_splits
 
     @property
     def use_patch_parallelism(self) -> bool:

@@ -1,6 +1,7 @@
 """Quick on-box kernel A/B: our gfx950 kernels vs the PyTorch-ROCm baselines.
 
 Run on an MI355X: python scripts/kernel_bench.py > gpurun_out/kernel_bench.json
+(--splitkv-only: just the split-KV attention sweep)
 """
 
 import os
@@ -28,12 +29,63 @@ def timeit(fn, iters=20, warmup=5):
     return (time.perf_counter() - t0) / iters * 1000  # ms
 
 
+def splitkv_sweep(results, reps=5, iters=100):
+    """Split-KV on the shapes whose plain grid (ceil(Lq/256) * B * H blocks)
+    leaves most of the 512 d64 block slots idle: S = 1, 2, 4, 8 and the
+    heuristic's choice, interleaved `reps` times per shape on the same box.
+    Reports the median and the min..max spread of the repeats."""
+    from distrifuser_amd import ops
+
+    dev = "cuda:0"
+    ext = ops.hip_ext()
+    shapes = [("chunked", h, lq, n) for h, lq, n in
+              [(10, 1024, 4), (20, 256, 4), (10, 7200, 8), (20, 3600, 4)]]
+    shapes += [("plain", h, l, 1) for h, l in [(20, 1024), (10, 4096)]]
+    for kind, h, lq, n in shapes:
+        lkv = lq * n
+        inner = h * 64
+        q = torch.randn(1, h, lq, 64, device=dev, dtype=torch.bfloat16)
+        if kind == "chunked":
+            slot = lq * 2 * inner
+            buf = torch.randn(n, slot + 64, device=dev, dtype=torch.bfloat16)
+            kv = buf[:, :slot].view(n, 1, lq, 2 * inner)
+            k = kv[..., :inner].unflatten(-1, (h, 64)).permute(1, 3, 0, 2, 4)
+            v = kv[..., inner:].unflatten(-1, (h, 64)).permute(1, 3, 0, 2, 4)
+        else:
+            k = torch.randn(1, h, lkv, 64, device=dev, dtype=torch.bfloat16)
+            v = torch.randn(1, h, lkv, 64, device=dev, dtype=torch.bfloat16)
+        auto = ops.attention_kv_splits(1, h, lq, lkv, 64, dev)
+        configs = [("S1", 1), ("S2", 2), ("S4", 4), ("S8", 8), ("auto", auto)]
+        ms = {name: [] for name, _ in configs}
+        for _ in range(reps):
+            for name, s in configs:
+                if s == 1:  # the entry the default path takes
+                    ms[name].append(timeit(lambda: ext.flash_attention(q, k, v), iters=iters))
+                else:
+                    ms[name].append(
+                        timeit(lambda: ext.flash_attention_ext(q, k, v, s, False), iters=iters))
+        row = {"op": "flash_attention_splitkv", "kind": kind, "heads": h, "Lq": lq, "Lkv": lkv,
+               "n_chunks": n, "blocks_S1": -(-lq // 256) * h, "auto_S": auto, "reps": reps}
+        for name, _ in configs:
+            t = sorted(ms[name])
+            row[f"ms_{name}"] = t[len(t) // 2]
+            row[f"spread_{name}"] = [t[0], t[-1]]
+        results.append(row)
+        print(json.dumps(row), flush=True)
+
+
 def main():
     assert torch.cuda.is_available()
     from distrifuser_amd import ops
 
     dev = "cuda:0"
     results = []
+
+    if "--splitkv-only" in sys.argv[1:]:
+        splitkv_sweep(results)
+        with open("kernel_bench_splitkv.json", "w") as f:
+            json.dump(results, f, indent=1)
+        return 0
 
     # ---- flash attention at SDXL shapes (B=1 CFG-split branch) ----
     #   (heads, L): 1024^2 -> (10, 4096) and (20, 1024)
@@ -76,6 +128,9 @@ def main():
             "tflops_sdpa_precat": flops / ms_sdpa / 1e9,
         })
         print(json.dumps(results[-1]), flush=True)
+
+    # ---- split-KV on the under-filled shapes ----
+    splitkv_sweep(results)
 
     # ---- implicit-GEMM conv3x3 at SDXL 3840^2 shapes (2-sample CFG batch) ----
     torch.backends.cudnn.benchmark = True
