@@ -1,4 +1,4 @@
-// Flash-attention forward, gfx950, bf16, head_dim 64 (K1/K2/K8 of SURVEY
+// Flash-attention forward, gfx950, bf16 or fp16, head_dim 64 (K1/K2/K8 of SURVEY
 // §2.4a): rectangular local-query x global-(stale)-KV attention.
 //
 // Structure (cdna_hip_programming.md §B "8-warp 32x32 ladder"; evolution and
@@ -102,6 +102,12 @@ __device__ __forceinline__ uint32_t cvt_pk_bf16(float a, float b) {
     asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
+// the fp16 twin: one instruction, round to nearest even, overflow to inf
+__device__ __forceinline__ uint32_t cvt_pk_f16(float a, float b) {
+    uint32_t r;
+    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
 
 __device__ __forceinline__ void lds_barrier() {
     // raw barrier with an LDS-only wait: unlike __syncthreads() it leaves
@@ -137,7 +143,10 @@ __device__ __forceinline__ float half_sum(float v) {
 // blockIdx.z selects one of gridDim.z tile-aligned slices of the KV range
 // (split-KV): with p.o_part set it writes its normalised partial output as
 // fp32 for merge_attn_kernel, otherwise (one split) bf16 O as the plain mode.
-template <int NW, int DPAD, bool DFULL, bool SPLIT, bool LSE>
+// F16: q/k/v/o are IEEE fp16 instead of bf16 — the two MFMAs, the P pack and
+// the output conversion change type; scores, max, sum, LSE and o_part stay
+// fp32 either way.
+template <int NW, int DPAD, bool DFULL, bool SPLIT, bool LSE, bool F16 = false>
 __global__ __launch_bounds__(NW * WAVE_SIZE)
 __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
     std::conditional_t<LSE, FlashAttnLseParams, FlashAttnParams> p, bool off32) {
@@ -370,7 +379,7 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
             const uint2 k1 = *reinterpret_cast<const uint2*>(ksrc + 8);
             const uint4 kk{k0.x, k0.y, k1.x, k1.y};
             const short8 kfrag = __builtin_bit_cast(short8, kk);
-            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfrag, qf[ks], s, 0, 0, 0);
+            s = mfma_32x32x16<F16>(kfrag, qf[ks], s);
         }
         __builtin_amdgcn_s_setprio(0);
         return s;
@@ -419,7 +428,7 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
             }
             l_run += half_sum(tsum);
 
-            // ---- pack P to bf16 B-fragments (guide T12: cvt_pk +
+            // ---- pack P to bf16 (fp16) B-fragments (guide T12: cvt_pk +
             // permlane32_swap); B frag j=0..7 -> P^T rows kt*16 + hi*8 + j.
             // Own word i holds regs {2i,2i+1} = rows {(2i&3)+8*(i>>1)+4*hi, +1}.
             // swap(a, b) leaves a = {lower: a, upper: lower's b} and
@@ -427,7 +436,9 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
             // apart gives hi=0 rows 0..7 and hi=1 rows 8..15 in order. ----
             uint32_t w[8];
 #pragma unroll
-            for (int i = 0; i < 8; ++i) w[i] = cvt_pk_bf16(pv[2 * i], pv[2 * i + 1]);
+            for (int i = 0; i < 8; ++i)
+                w[i] = F16 ? cvt_pk_f16(pv[2 * i], pv[2 * i + 1])
+                           : cvt_pk_bf16(pv[2 * i], pv[2 * i + 1]);
             short8 pb[2];
 #pragma unroll
             for (int kt = 0; kt < 2; ++kt) {
@@ -452,7 +463,7 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
                     const short4v v1 =
                         __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_short4v*)(vsrc + 4 * V_ROW));
                     const short8 vf = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-                    ot[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pb[kt], ot[dt], 0, 0, 0);
+                    ot[dt] = mfma_32x32x16<F16>(vf, pb[kt], ot[dt]);
                 }
             }
             __builtin_amdgcn_s_setprio(0);
@@ -533,11 +544,15 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
         uint32_t ow[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            const uint32_t e0 =
-                __builtin_bit_cast(uint16_t, __float2bfloat16(ot[dt][2 * i] * inv));
-            const uint32_t e1 =
-                __builtin_bit_cast(uint16_t, __float2bfloat16(ot[dt][2 * i + 1] * inv));
-            ow[i] = e0 | (e1 << 16);
+            if constexpr (F16) {
+                ow[i] = cvt_pk_f16(ot[dt][2 * i] * inv, ot[dt][2 * i + 1] * inv);
+            } else {
+                const uint32_t e0 =
+                    __builtin_bit_cast(uint16_t, __float2bfloat16(ot[dt][2 * i] * inv));
+                const uint32_t e1 =
+                    __builtin_bit_cast(uint16_t, __float2bfloat16(ot[dt][2 * i + 1] * inv));
+                ow[i] = e0 | (e1 << 16);
+            }
         }
 #pragma unroll
         for (int g = 0; g < 4; g += 2) {
@@ -557,11 +572,11 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
 namespace {
 
 // ---- merge of split-KV partials --------------------------------------------
-// One thread per (row, 8 d): S x two 16 B fp32 loads, one 16 B bf16 store (or
+// One thread per (row, 8 d): S x two 16 B fp32 loads, one 16 B bf16/fp16 store (or
 // two fp32). Plain HBM-bound streaming; the S weights of a row are re-derived
 // by each of its Dh/8 threads from the (cached) lse parts. Fixed summation
 // order s = 0..S-1, no atomics.
-template <bool OUT_BF16>
+template <int OUT>  // DfaDtype of the output
 __global__ __launch_bounds__(256) void merge_attn_kernel(MergeAttnParams p) {
     const int dcols = p.Dh / 8;
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -597,12 +612,12 @@ __global__ __launch_bounds__(256) void merge_attn_kernel(MergeAttnParams p) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc[j] *= inv;
     }
-    if (OUT_BF16) {
+    if (OUT != DFA_F32) {
         uint32_t w[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const uint32_t e0 = __builtin_bit_cast(uint16_t, __float2bfloat16(acc[2 * j]));
-            const uint32_t e1 = __builtin_bit_cast(uint16_t, __float2bfloat16(acc[2 * j + 1]));
+            const uint32_t e0 = f32_to_b16<OUT == DFA_F16>(acc[2 * j]);
+            const uint32_t e1 = f32_to_b16<OUT == DFA_F16>(acc[2 * j + 1]);
             w[j] = e0 | (e1 << 16);
         }
         *reinterpret_cast<uint4*>(static_cast<uint16_t*>(p.out) + row * p.Dh + dc * 8) =
@@ -622,10 +637,12 @@ void launch_merge_attention(const MergeAttnParams& p, hipStream_t stream) {
     const int64_t total = (int64_t)p.B * p.Lq * p.H * (p.Dh / 8);
     if (total == 0) return;
     const dim3 grid((unsigned)((total + 255) / 256));
-    if (p.out_bf16)
-        merge_attn_kernel<true><<<grid, 256, 0, stream>>>(p);
+    if (p.out_dtype == DFA_BF16)
+        merge_attn_kernel<DFA_BF16><<<grid, 256, 0, stream>>>(p);
+    else if (p.out_dtype == DFA_F16)
+        merge_attn_kernel<DFA_F16><<<grid, 256, 0, stream>>>(p);
     else
-        merge_attn_kernel<false><<<grid, 256, 0, stream>>>(p);
+        merge_attn_kernel<DFA_F32><<<grid, 256, 0, stream>>>(p);
 }
 
 namespace {
@@ -639,7 +656,7 @@ bool fits_off32(const FlashAttnParams& p) {
     return sl >= 0 && sl * 2 * KVB + DPAD * 2 <= (int64_t)INT32_MAX;
 }
 
-template <int DPAD>
+template <int DPAD, bool F16>
 void launch_dpad_lse(const FlashAttnLseParams& p, int splits, hipStream_t stream) {
     constexpr int NW = 8;
     const int qblk = QW * NW;
@@ -647,14 +664,16 @@ void launch_dpad_lse(const FlashAttnLseParams& p, int splits, hipStream_t stream
     dim3 block(NW * WAVE_SIZE);
     const bool off32 = fits_off32<DPAD>(p);
     if (p.Dh == DPAD)
-        flash_attn_kernel<NW, DPAD, true, SPLIT_STAGE, true><<<grid, block, 0, stream>>>(p, off32);
+        flash_attn_kernel<NW, DPAD, true, SPLIT_STAGE, true, F16>
+            <<<grid, block, 0, stream>>>(p, off32);
     else
-        flash_attn_kernel<NW, DPAD, false, SPLIT_STAGE, true><<<grid, block, 0, stream>>>(p, off32);
+        flash_attn_kernel<NW, DPAD, false, SPLIT_STAGE, true, F16>
+            <<<grid, block, 0, stream>>>(p, off32);
 }
 
 }  // namespace
 
-template <int DPAD>
+template <int DPAD, bool F16>
 static void launch_dpad(const FlashAttnParams& p, hipStream_t stream) {
     constexpr int NW = 8;
     const int qblk = QW * NW;
@@ -662,23 +681,33 @@ static void launch_dpad(const FlashAttnParams& p, hipStream_t stream) {
     dim3 block(NW * WAVE_SIZE);
     const bool off32 = fits_off32<DPAD>(p);
     if (p.Dh == DPAD)
-        flash_attn_kernel<NW, DPAD, true, SPLIT_STAGE, false><<<grid, block, 0, stream>>>(p, off32);
+        flash_attn_kernel<NW, DPAD, true, SPLIT_STAGE, false, F16>
+            <<<grid, block, 0, stream>>>(p, off32);
     else
-        flash_attn_kernel<NW, DPAD, false, SPLIT_STAGE, false><<<grid, block, 0, stream>>>(p, off32);
+        flash_attn_kernel<NW, DPAD, false, SPLIT_STAGE, false, F16>
+            <<<grid, block, 0, stream>>>(p, off32);
 }
 
-void launch_flash_attention_d64(const FlashAttnParams& p, hipStream_t stream) {
+template <bool F16>
+static void launch_plain(const FlashAttnParams& p, hipStream_t stream) {
     // 8-wave (256-row) blocks measured best across the SD-family shapes;
     // every Lkv takes 128-token tiles plus a peeled tail. DPAD covers the
     // SD-family head dims.
     if (p.Dh <= 64)
-        launch_dpad<64>(p, stream);
+        launch_dpad<64, F16>(p, stream);
     else if (p.Dh <= 96)
-        launch_dpad<96>(p, stream);
+        launch_dpad<96, F16>(p, stream);
     else if (p.Dh <= 128)
-        launch_dpad<128>(p, stream);
+        launch_dpad<128, F16>(p, stream);
     else
-        launch_dpad<160>(p, stream);
+        launch_dpad<160, F16>(p, stream);
+}
+
+void launch_flash_attention_d64(const FlashAttnParams& p, int dtype, hipStream_t stream) {
+    if (dtype == DFA_F16)
+        launch_plain<true>(p, stream);
+    else
+        launch_plain<false>(p, stream);
 }
 
 int flash_attention_num_splits(int64_t lkv, int splits) {
@@ -686,16 +715,25 @@ int flash_attention_num_splits(int64_t lkv, int splits) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(splits, tiles));
 }
 
-void launch_flash_attention_lse(const FlashAttnLseParams& p, int splits, hipStream_t stream) {
-    splits = flash_attention_num_splits(p.NC * p.LC, splits);
+template <bool F16>
+static void launch_lse(const FlashAttnLseParams& p, int splits, hipStream_t stream) {
     if (p.Dh <= 64)
-        launch_dpad_lse<64>(p, splits, stream);
+        launch_dpad_lse<64, F16>(p, splits, stream);
     else if (p.Dh <= 96)
-        launch_dpad_lse<96>(p, splits, stream);
+        launch_dpad_lse<96, F16>(p, splits, stream);
     else if (p.Dh <= 128)
-        launch_dpad_lse<128>(p, splits, stream);
+        launch_dpad_lse<128, F16>(p, splits, stream);
     else
-        launch_dpad_lse<160>(p, splits, stream);
+        launch_dpad_lse<160, F16>(p, splits, stream);
+}
+
+void launch_flash_attention_lse(const FlashAttnLseParams& p, int splits, int dtype,
+                                hipStream_t stream) {
+    splits = flash_attention_num_splits(p.NC * p.LC, splits);
+    if (dtype == DFA_F16)
+        launch_lse<true>(p, splits, stream);
+    else
+        launch_lse<false>(p, splits, stream);
 }
 
 // ---- fragment-layout probes (tests/test_ops_gpu.py) ------------------------

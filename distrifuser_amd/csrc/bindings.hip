@@ -19,6 +19,11 @@ int dtype_of(const at::Tensor& t) {
     }
 }
 
+// the MFMA kernels and LayerNorm take bf16 or fp16 (a template axis each)
+bool is_b16(const at::Tensor& t) {
+    return t.scalar_type() == at::kBFloat16 || t.scalar_type() == at::kHalf;
+}
+
 hipStream_t cur_stream() { return at::hip::getCurrentHIPStream().stream(); }
 
 at::Tensor group_norm_stats(const at::Tensor& x_, int64_t num_groups) {
@@ -146,7 +151,11 @@ at::Tensor cfg_affine_step(const at::Tensor& noise, const at::Tensor& x, double 
 // q: [B,H,Lq,D]; k/v: [B,H,Lkv,D] or [B,H,NC,LC,D] (stale-KV chunks): checks
 // and everything of FlashAttnParams but the output pointer
 FlashAttnParams flash_params(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v) {
-    TORCH_CHECK(q.is_cuda() && q.scalar_type() == at::kBFloat16, "flash_attention: bf16 only");
+    TORCH_CHECK(q.is_cuda() && is_b16(q), "flash_attention: bf16 or fp16 only");
+    TORCH_CHECK(k.scalar_type() == q.scalar_type(), "flash_attention: k must have q's dtype (",
+                q.scalar_type(), "), got ", k.scalar_type());
+    TORCH_CHECK(v.scalar_type() == q.scalar_type(), "flash_attention: v must have q's dtype (",
+                q.scalar_type(), "), got ", v.scalar_type());
     const int Dh = (int)q.size(-1);
     TORCH_CHECK(q.dim() == 4 && Dh % 8 == 0 && Dh <= 160,
                 "head_dim must be a multiple of 8 and <= 160");
@@ -168,7 +177,6 @@ FlashAttnParams flash_params(const at::Tensor& q, const at::Tensor& k, const at:
 
     auto set_kv = [&](const at::Tensor& t, const uint16_t*& ptr, int64_t& sb, int64_t& sh,
                       int64_t& sc, int64_t& sl, int64_t& NC, int64_t& LC) {
-        TORCH_CHECK(t.scalar_type() == at::kBFloat16);
         TORCH_CHECK((int)t.size(-1) == Dh, "k/v head_dim mismatch");
         ptr = reinterpret_cast<const uint16_t*>(t.data_ptr());
         sb = t.stride(0);
@@ -203,7 +211,7 @@ at::Tensor flash_attention(const at::Tensor& q, const at::Tensor& k, const at::T
     FlashAttnParams p = flash_params(q, k, v);
     auto o = at::empty({(long)p.B, (long)p.Lq, (long)p.H, (long)p.Dh}, q.options());
     p.o = reinterpret_cast<uint16_t*>(o.data_ptr());
-    launch_flash_attention_d64(p, cur_stream());
+    launch_flash_attention_d64(p, dtype_of(q), cur_stream());
     return o.permute({0, 2, 1, 3});  // logical [B,H,Lq,64]
 }
 
@@ -225,12 +233,13 @@ int64_t flash_attention_partial(const at::Tensor& q, const at::Tensor& k, const 
                 "lse_part must be contiguous fp32 [S,B,H,Lq] with S = ", S);
     p.o_part = o_part.data_ptr<float>();
     p.lse = lse_part.data_ptr<float>();
-    launch_flash_attention_lse(p, S, cur_stream());
+    launch_flash_attention_lse(p, S, dtype_of(q), cur_stream());
     return S;
 }
 
 at::Tensor merge_attention_into(const at::Tensor& o_parts, const at::Tensor& lse_parts,
-                                bool out_bf16, const c10::optional<at::Tensor>& lse_out) {
+                                at::ScalarType out_dtype,
+                                const c10::optional<at::Tensor>& lse_out) {
     TORCH_CHECK(o_parts.is_cuda() && o_parts.dim() == 5 && o_parts.scalar_type() == at::kFloat &&
                     o_parts.is_contiguous(),
                 "merge_attention: o_parts must be contiguous fp32 [S,B,Lq,H,D]");
@@ -247,23 +256,28 @@ at::Tensor merge_attention_into(const at::Tensor& o_parts, const at::Tensor& lse
                         (at::IntArrayRef{(long)m.S, (long)m.B, (long)m.H, (long)m.Lq}),
                 "merge_attention: lse_parts must be contiguous fp32 [S,B,H,Lq]");
     auto out = at::empty({(long)m.B, (long)m.Lq, (long)m.H, (long)m.Dh},
-                         o_parts.options().dtype(out_bf16 ? at::kBFloat16 : at::kFloat));
+                         o_parts.options().dtype(out_dtype));
     m.o_parts = o_parts.data_ptr<float>();
     m.lse_parts = lse_parts.data_ptr<float>();
     m.out = out.data_ptr();
-    m.out_bf16 = out_bf16;
+    m.out_dtype = dtype_of(out);
     if (lse_out.has_value()) m.lse = lse_out->data_ptr<float>();
     launch_merge_attention(m, cur_stream());
     return out;
 }
 
-// parts stacked on dim 0 -> (out [B,Lq,H,D] bf16 or fp32, lse [B,H,Lq])
+// parts stacked on dim 0 -> (out [B,Lq,H,D], lse [B,H,Lq]). out is bf16 or
+// fp32 by out_bf16 unless out_dtype names one of bf16 / fp16 / fp32.
 std::vector<at::Tensor> merge_attention(const at::Tensor& o_parts, const at::Tensor& lse_parts,
-                                        bool out_bf16) {
+                                        bool out_bf16,
+                                        const c10::optional<at::ScalarType>& out_dtype) {
+    const at::ScalarType dt = out_dtype.value_or(out_bf16 ? at::kBFloat16 : at::kFloat);
+    TORCH_CHECK(dt == at::kBFloat16 || dt == at::kHalf || dt == at::kFloat,
+                "merge_attention: out_dtype must be bf16, fp16 or fp32");
     TORCH_CHECK(lse_parts.dim() == 4, "merge_attention: lse_parts must be [S,B,H,Lq]");
     auto lse = at::empty({lse_parts.size(1), lse_parts.size(2), lse_parts.size(3)},
                          lse_parts.options());
-    auto out = merge_attention_into(o_parts, lse_parts, out_bf16, lse);
+    auto out = merge_attention_into(o_parts, lse_parts, dt, lse);
     return {out, lse};
 }
 
@@ -284,23 +298,25 @@ std::vector<at::Tensor> flash_attention_ext(const at::Tensor& q, const at::Tenso
         auto o = at::empty({B, Lq, H, Dh}, q.options());
         p.o = reinterpret_cast<uint16_t*>(o.data_ptr());
         if (!return_lse) {
-            launch_flash_attention_d64(p, cur_stream());
+            launch_flash_attention_d64(p, dtype_of(q), cur_stream());
             return {o.permute({0, 2, 1, 3})};
         }
         auto lse = at::empty({B, H, Lq}, f32);
         p.lse = lse.data_ptr<float>();
-        launch_flash_attention_lse(p, 1, cur_stream());
+        launch_flash_attention_lse(p, 1, dtype_of(q), cur_stream());
         return {o.permute({0, 2, 1, 3}), lse};
     }
     auto o_part = at::empty({(long)S, B, Lq, H, Dh}, f32);
     auto lse_part = at::empty({(long)S, B, H, Lq}, f32);
     p.o_part = o_part.data_ptr<float>();
     p.lse = lse_part.data_ptr<float>();
-    launch_flash_attention_lse(p, S, cur_stream());
+    launch_flash_attention_lse(p, S, dtype_of(q), cur_stream());
+    // the merge writes the input dtype
     if (!return_lse)
-        return {merge_attention_into(o_part, lse_part, true, c10::nullopt).permute({0, 2, 1, 3})};
+        return {merge_attention_into(o_part, lse_part, q.scalar_type(), c10::nullopt)
+                    .permute({0, 2, 1, 3})};
     auto lse = at::empty({B, H, Lq}, f32);
-    auto o = merge_attention_into(o_part, lse_part, true, lse);
+    auto o = merge_attention_into(o_part, lse_part, q.scalar_type(), lse);
     return {o.permute({0, 2, 1, 3}), lse};
 }
 
@@ -309,13 +325,15 @@ at::Tensor conv3x3(const at::Tensor& x, const at::Tensor& wp,
                    const c10::optional<at::Tensor>& top, const c10::optional<at::Tensor>& bot,
                    const c10::optional<at::Tensor>& residual,
                    const c10::optional<at::Tensor>& bias2) {
-    TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.scalar_type() == at::kBFloat16,
-                "x must be CUDA bf16 [B,Cin,H,W]");
+    TORCH_CHECK(x.is_cuda() && x.dim() == 4 && is_b16(x),
+                "x must be CUDA bf16 or fp16 [B,Cin,H,W]");
+    const auto dt = x.scalar_type();
     TORCH_CHECK(x.stride(3) == 1 && x.stride(2) == x.size(3), "x rows must be contiguous");
-    TORCH_CHECK(wp.is_cuda() && wp.dim() == 5 && wp.is_contiguous() &&
-                wp.scalar_type() == at::kBFloat16 && wp.size(0) == 9 &&
+    TORCH_CHECK(wp.is_cuda() && wp.dim() == 5 && wp.is_contiguous() && wp.size(0) == 9 &&
                 wp.size(3) == 64 && wp.size(4) == 8,
-                "wp must be packed [9][KS][CT][64][8] bf16");
+                "wp must be packed [9][KS][CT][64][8]");
+    TORCH_CHECK(wp.scalar_type() == dt, "conv3x3: wp must have x's dtype (", dt, "), got ",
+                wp.scalar_type());
     TORCH_CHECK(stride == 1 || stride == 2);
     const int B = (int)x.size(0), Cin = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3);
     const int Ho = (H - 1) / (int)stride + 1, Wo = (W - 1) / (int)stride + 1;
@@ -338,7 +356,9 @@ at::Tensor conv3x3(const at::Tensor& x, const at::Tensor& wp,
     if (const char* dbg = getenv("DFA_CONV_DEBUG")) p.debug = atoi(dbg);
     at::Tensor bias_c;
     if (bias.has_value()) {
-        bias_c = bias->to(at::kBFloat16).contiguous();
+        TORCH_CHECK(bias->scalar_type() == dt || !is_b16(*bias),
+                    "conv3x3: bias must have x's dtype (", dt, "), got ", bias->scalar_type());
+        bias_c = bias->to(dt).contiguous();
         TORCH_CHECK(bias_c.numel() == cout);
         p.bias = reinterpret_cast<const uint16_t*>(bias_c.data_ptr());
     }
@@ -346,9 +366,10 @@ at::Tensor conv3x3(const at::Tensor& x, const at::Tensor& wp,
                         int64_t& sc) {
         if (!h.has_value()) return;
         const at::Tensor& t = *h;
-        TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 && t.stride(-1) == 1 &&
-                    t.size(-1) == W && t.size(1) == Cin,
-                    "halo must be bf16 [B,Cin,(1,)W] with contiguous rows");
+        TORCH_CHECK(t.scalar_type() == dt, "conv3x3: top/bot halo must have x's dtype (", dt,
+                    "), got ", t.scalar_type());
+        TORCH_CHECK(t.is_cuda() && t.stride(-1) == 1 && t.size(-1) == W && t.size(1) == Cin,
+                    "halo must be [B,Cin,(1,)W] with contiguous rows");
         ptr = reinterpret_cast<const uint16_t*>(t.data_ptr());
         sb = t.stride(0);
         sc = t.stride(1);
@@ -357,22 +378,25 @@ at::Tensor conv3x3(const at::Tensor& x, const at::Tensor& wp,
     set_halo(bot, p.bot, p.b_sb, p.b_sc);
     at::Tensor b2_c;
     if (bias2.has_value()) {
-        b2_c = bias2->to(at::kBFloat16).contiguous();
+        TORCH_CHECK(bias2->scalar_type() == dt || !is_b16(*bias2),
+                    "conv3x3: bias2 must have x's dtype (", dt, "), got ", bias2->scalar_type());
+        b2_c = bias2->to(dt).contiguous();
         TORCH_CHECK(b2_c.numel() == (int64_t)B * cout, "bias2 must be [B, Cout]");
         p.bias2 = reinterpret_cast<const uint16_t*>(b2_c.data_ptr());
     }
     at::Tensor res_c;
     if (residual.has_value()) {
         res_c = residual->contiguous();
-        TORCH_CHECK(res_c.scalar_type() == at::kBFloat16 &&
-                    res_c.sizes() == (at::IntArrayRef{(long)B, (long)cout, (long)Ho, (long)Wo}),
-                    "residual must be bf16 [B,Cout,Ho,Wo]");
+        TORCH_CHECK(res_c.scalar_type() == dt, "conv3x3: residual must have x's dtype (", dt,
+                    "), got ", res_c.scalar_type());
+        TORCH_CHECK(res_c.sizes() == (at::IntArrayRef{(long)B, (long)cout, (long)Ho, (long)Wo}),
+                    "residual must be [B,Cout,Ho,Wo]");
         p.residual = reinterpret_cast<const uint16_t*>(res_c.data_ptr());
     }
 
     auto o = at::empty({(long)B, (long)cout, (long)Ho, (long)Wo}, x.options());
     p.o = reinterpret_cast<uint16_t*>(o.data_ptr());
-    launch_conv3x3(p, (int)stride, cur_stream());
+    launch_conv3x3(p, (int)stride, dtype_of(x), cur_stream());
     return o;
 }
 
@@ -402,41 +426,54 @@ std::vector<at::Tensor> cfg_dpm_step(const at::Tensor& noise, const at::Tensor& 
     return {out, x0};
 }
 
+// LayerNorm affine parameter in x's dtype: an fp32 master copy is cast as it
+// always was, the other 16-bit type is a mix-up
+at::Tensor ln_param(const at::Tensor& t, const at::Tensor& x, const char* op, const char* name) {
+    TORCH_CHECK(t.scalar_type() == x.scalar_type() || !is_b16(t), op, ": ", name,
+                " must have x's dtype (", x.scalar_type(), "), got ", t.scalar_type());
+    return t.to(x.scalar_type()).contiguous();
+}
+
 at::Tensor layer_norm(const at::Tensor& x_, const at::Tensor& w_, const at::Tensor& b_,
                       double eps) {
-    TORCH_CHECK(x_.is_cuda() && x_.scalar_type() == at::kBFloat16);
+    TORCH_CHECK(x_.is_cuda() && is_b16(x_), "layer_norm: bf16 or fp16 only");
     auto x = x_.contiguous();
     const int C = (int)x.size(-1);
     TORCH_CHECK(C % 8 == 0 && C <= 2048, "layer_norm kernel: C % 8 == 0 and C <= 2048");
-    auto w = w_.to(at::kBFloat16).contiguous();
-    auto b = b_.to(at::kBFloat16).contiguous();
+    auto w = ln_param(w_, x, "layer_norm", "weight");
+    auto b = ln_param(b_, x, "layer_norm", "bias");
     auto y = at::empty_like(x);
     launch_layer_norm(x.data_ptr(), nullptr, y.data_ptr(), nullptr, w.data_ptr(), b.data_ptr(),
-                      (float)eps, x.numel() / C, C, cur_stream());
+                      (float)eps, x.numel() / C, C, dtype_of(x), cur_stream());
     return y;
 }
 
 std::vector<at::Tensor> add_layer_norm(const at::Tensor& x_, const at::Tensor& res_,
                                        const at::Tensor& w_, const at::Tensor& b_, double eps) {
-    TORCH_CHECK(x_.is_cuda() && x_.scalar_type() == at::kBFloat16);
+    TORCH_CHECK(x_.is_cuda() && is_b16(x_), "add_layer_norm: bf16 or fp16 only");
     auto x = x_.contiguous();
     auto res = res_.contiguous();
-    TORCH_CHECK(res.sizes() == x.sizes() && res.scalar_type() == at::kBFloat16);
+    TORCH_CHECK(res.scalar_type() == x.scalar_type(), "add_layer_norm: res must have x's dtype (",
+                x.scalar_type(), "), got ", res.scalar_type());
+    TORCH_CHECK(res.sizes() == x.sizes());
     const int C = (int)x.size(-1);
     TORCH_CHECK(C % 8 == 0 && C <= 2048, "add_layer_norm kernel: C % 8 == 0 and C <= 2048");
-    auto w = w_.to(at::kBFloat16).contiguous();
-    auto b = b_.to(at::kBFloat16).contiguous();
+    auto w = ln_param(w_, x, "add_layer_norm", "weight");
+    auto b = ln_param(b_, x, "add_layer_norm", "bias");
     auto y = at::empty_like(x);
     auto sum = at::empty_like(x);
     launch_layer_norm(x.data_ptr(), res.data_ptr(), y.data_ptr(), sum.data_ptr(), w.data_ptr(),
-                      b.data_ptr(), (float)eps, x.numel() / C, C, cur_stream());
+                      b.data_ptr(), (float)eps, x.numel() / C, C, dtype_of(x), cur_stream());
     return {sum, y};
 }
 
 at::Tensor vae_attention(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v) {
-    TORCH_CHECK(q.is_cuda() && q.dim() == 3 && q.size(-1) == 512 &&
-                q.scalar_type() == at::kBFloat16,
-                "vae_attention: bf16 [B, L, 512] only");
+    TORCH_CHECK(q.is_cuda() && q.dim() == 3 && q.size(-1) == 512 && is_b16(q),
+                "vae_attention: bf16 or fp16 [B, L, 512] only");
+    TORCH_CHECK(k.scalar_type() == q.scalar_type(), "vae_attention: k must have q's dtype (",
+                q.scalar_type(), "), got ", k.scalar_type());
+    TORCH_CHECK(v.scalar_type() == q.scalar_type(), "vae_attention: v must have q's dtype (",
+                q.scalar_type(), "), got ", v.scalar_type());
     auto qc = q.contiguous(), kc = k.contiguous(), vc = v.contiguous();
     TORCH_CHECK(kc.sizes() == qc.sizes() && vc.sizes() == qc.sizes());
     VaeAttnParams p{};
@@ -449,7 +486,7 @@ at::Tensor vae_attention(const at::Tensor& q, const at::Tensor& k, const at::Ten
     p.scale = 1.0f / std::sqrt(512.0f);
     auto o = at::empty_like(qc);
     p.o = reinterpret_cast<uint16_t*>(o.data_ptr());
-    launch_vae_attention(p, cur_stream());
+    launch_vae_attention(p, dtype_of(q), cur_stream());
     return o;
 }
 
@@ -489,7 +526,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gn_merge_stats", &gn_merge_stats,
           "merge stale peer GN moments with fresh local ones (one launch)");
     m.def("cfg_affine_step", &cfg_affine_step, "fused CFG combine + affine scheduler update");
-    m.def("flash_attention", &flash_attention, "bf16 d64 flash attention (chunked stale KV)");
+    m.def("flash_attention", &flash_attention, "bf16/fp16 flash attention (chunked stale KV)");
     m.def("flash_attention_ext", &flash_attention_ext,
           "flash attention with split-KV and optional log-sum-exp -> [out] or [out, lse]",
           pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"),
@@ -498,13 +535,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "split-KV partials into caller buffers (o_part fp32 [S,B,Lq,H,D], lse_part [S,B,H,Lq])");
     m.def("merge_attention", &merge_attention,
           "merge fp32 attention partials by their log-sum-exp -> [out, lse]",
-          pybind11::arg("o_parts"), pybind11::arg("lse_parts"), pybind11::arg("out_bf16") = true);
+          pybind11::arg("o_parts"), pybind11::arg("lse_parts"), pybind11::arg("out_bf16") = true,
+          pybind11::arg("out_dtype") = pybind11::none());
     m.def("cfg_dpm_step", &cfg_dpm_step, "fused CFG + DPM-Solver++(2M) update -> (prev, x0)");
-    m.def("layer_norm", &layer_norm, "bf16 fused LayerNorm");
-    m.def("add_layer_norm", &add_layer_norm, "bf16 fused residual-add + LayerNorm -> (sum, y)");
-    m.def("vae_attention", &vae_attention, "bf16 single-head d=512 VAE mid attention");
+    m.def("layer_norm", &layer_norm, "bf16/fp16 fused LayerNorm");
+    m.def("add_layer_norm", &add_layer_norm, "bf16/fp16 fused residual-add + LayerNorm -> (sum, y)");
+    m.def("vae_attention", &vae_attention, "bf16/fp16 single-head d=512 VAE mid attention");
     m.def("conv3x3", &conv3x3,
-          "bf16 implicit-GEMM 3x3 conv, stride 1/2, in-place halo rows");
+          "bf16/fp16 implicit-GEMM 3x3 conv, stride 1/2, in-place halo rows");
     m.def("mfma_probe", &mfma_probe, "dump mfma_f32_16x16x32_bf16 fragment mapping");
     m.def("mfma_probe32", &mfma_probe32, "dump mfma_f32_32x32x16_bf16 fragment mapping");
 }

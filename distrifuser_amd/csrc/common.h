@@ -27,6 +27,37 @@ __device__ __forceinline__ f16_t from_f32<f16_t>(float v) { return __float2half(
 template <>
 __device__ __forceinline__ float from_f32<float>(float v) { return v; }
 
+// ---- the 16-bit element type of the MFMA kernels ----------------------------
+// F16 = false: bf16, true: IEEE fp16. A compile-time axis only: the bf16
+// instantiations expand to exactly the code they had before it existed.
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef float float16v_ __attribute__((ext_vector_type(16)));
+
+template <bool F16>
+__device__ __forceinline__ float16v_ mfma_32x32x16(short8 a, short8 b, float16v_ c) {
+    if constexpr (F16)
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, a),
+                                                      __builtin_bit_cast(half8, b), c, 0, 0, 0);
+    else
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+
+// fp32 -> 16 bits, round to nearest even; fp16 overflows to inf (no saturation)
+template <bool F16>
+__device__ __forceinline__ uint16_t f32_to_b16(float v) {
+    if constexpr (F16)
+        return __builtin_bit_cast(uint16_t, __float2half(v));
+    else
+        return __builtin_bit_cast(uint16_t, __float2bfloat16(v));
+}
+template <bool F16>
+__device__ __forceinline__ float b16_to_f32(uint16_t v) {
+    if constexpr (F16)
+        return to_f32(__builtin_bit_cast(f16_t, v));
+    else
+        return to_f32(__builtin_bit_cast(bf16_t, v));
+}
+
 // elements per 16-byte vector
 template <typename T>
 struct VecN {
@@ -133,6 +164,10 @@ __device__ __forceinline__ uint4 transpose8x8_bf16(uint4 v, int lane) {
         }
     }
     return uint4{d[0], d[1], d[2], d[3]};
+}
+// the butterfly moves 16-bit words and never looks inside them: fp16 rides it
+__device__ __forceinline__ uint4 transpose8x8_b16(uint4 v, int lane) {
+    return transpose8x8_bf16(v, lane);
 }
 
 

@@ -1,4 +1,4 @@
-// Implicit-GEMM 3x3 convolution, gfx950, bf16, NCHW (K4/K5/K10 of SURVEY
+// Implicit-GEMM 3x3 convolution, gfx950, bf16 or fp16, NCHW (K4/K5/K10 of SURVEY
 // §2.4a): per-tap GEMM accumulation — the conv is 9 shifted GEMMs
 // O^T[cout][pix] += W^T_tap[cout][cin] x I[cin][pix + tap-shift] — so no
 // im2col materialization and no torch.cat/F.pad halo assembly (the
@@ -67,7 +67,9 @@ __device__ __forceinline__ int32x4_ck make_srsrc(const void* base, uint32_t byte
 //   across cout-blocks; 8 B-padded LDS rows (stride 72 B, gcd(18,32)=2)
 //   make fragment reads 2-way instead of 8-way conflicted as b64 pairs;
 //   load bursts are issued in arrays before the transpose+write pass.
-template <int S, int YB, int XW, int CIN_T, int NCT, int PW>
+// F16: every 16-bit tensor is IEEE fp16 instead of bf16 (the MFMA and the
+// epilogue conversions change type; staging moves 16-bit words either way).
+template <int S, int YB, int XW, int CIN_T, int NCT, int PW, bool F16 = false>
 __global__ __launch_bounds__(YB * XW * WAVE_SIZE) void conv3x3_kernel(Conv3x3Params p) {
     constexpr int NW = YB * XW;
     constexpr int XB = XW * 32 * PW;
@@ -274,7 +276,7 @@ __global__ __launch_bounds__(YB * XW * WAVE_SIZE) void conv3x3_kernel(Conv3x3Par
                     raw = *reinterpret_cast<const uint4*>(vals);
                 }
             }
-            const uint4 tr = transpose8x8_bf16(raw, lane);
+            const uint4 tr = transpose8x8_b16(raw, lane);
             const int xi = 1 + xw * 8 + gr;  // lane now owns x = xi
             if (xi < XIN) {
                 const int plane = (S == 1) ? 0 : (xi & 1);
@@ -333,8 +335,8 @@ __global__ __launch_bounds__(YB * XW * WAVE_SIZE) void conv3x3_kernel(Conv3x3Par
                             &wb[(((tap * KS_T + ks2) * NCT + ct2) * WAVE_SIZE + lane) * 16]);
 #pragma unroll
                         for (int px = 0; px < PW; ++px)
-                            acc[ct2][px] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                                afrag, bfrag[px], acc[ct2][px], 0, 0, 0);
+                            acc[ct2][px] =
+                                mfma_32x32x16<F16>(afrag, bfrag[px], acc[ct2][px]);
                     }
                 }
             }
@@ -379,15 +381,11 @@ __global__ __launch_bounds__(YB * XW * WAVE_SIZE) void conv3x3_kernel(Conv3x3Par
                 const int cout = ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
                 if (cout < p.Cout) {
                     float v = acc[ct2][px][r];
-                    if (p.bias) v += to_f32(reinterpret_cast<const bf16_t*>(p.bias)[cout]);
-                    if (p.bias2)
-                        v += to_f32(reinterpret_cast<const bf16_t*>(
-                            p.bias2)[b * p.Cout + cout]);
-                    if (rbase)
-                        v += to_f32(reinterpret_cast<const bf16_t*>(
-                            rbase)[(int64_t)cout * p.Ho * p.Wo]);
-                    obase[(int64_t)cout * p.Ho * p.Wo] =
-                        __builtin_bit_cast(uint16_t, __float2bfloat16(v));
+                    if (p.bias) v += b16_to_f32<F16>(p.bias[cout]);
+                    if (p.bias2) v += b16_to_f32<F16>(p.bias2[b * p.Cout + cout]);
+                    if (rbase) v += b16_to_f32<F16>(rbase[(int64_t)cout * p.Ho * p.Wo]);
+                    // fp16: IEEE round-to-nearest-even, beyond 65504 -> inf
+                    obase[(int64_t)cout * p.Ho * p.Wo] = f32_to_b16<F16>(v);
                 }
             }
         }
@@ -396,7 +394,8 @@ __global__ __launch_bounds__(YB * XW * WAVE_SIZE) void conv3x3_kernel(Conv3x3Par
 
 }  // namespace
 
-void launch_conv3x3(const Conv3x3Params& p, int stride, hipStream_t stream) {
+template <bool F16>
+static void launch_conv3x3_t(const Conv3x3Params& p, int stride, hipStream_t stream) {
     if (stride == 1) {
         // 8 waves: 8 output rows x 1 x-wave of 64 px (PW=2 A-frag reuse),
         // 128 couts per block (NCT=4 halves the input re-read);
@@ -420,11 +419,12 @@ void launch_conv3x3(const Conv3x3Params& p, int stride, hipStream_t stream) {
             const int npix2 = nxb2 * nyb2 * p.B;
             const int ncb2 = (p.CT + NCT2 - 1) / NCT2;
             dim3 g2((unsigned)(8 * ncb2 * ((npix2 + 7) / 8)));
-            conv3x3_kernel<1, YB2, XW2, 16, NCT2, PW2>
+            conv3x3_kernel<1, YB2, XW2, 16, NCT2, PW2, F16>
                 <<<g2, dim3(YB2 * XW2 * WAVE_SIZE), 0, stream>>>(p);
             return;
         }
-        conv3x3_kernel<1, YB, XW, 16, NCT, PW><<<grid, dim3(YB * XW * WAVE_SIZE), 0, stream>>>(p);
+        conv3x3_kernel<1, YB, XW, 16, NCT, PW, F16>
+            <<<grid, dim3(YB * XW * WAVE_SIZE), 0, stream>>>(p);
     } else {
         // stride 2: 8 waves: 4 output rows x 2 x-waves of 32 px;
         // LDS (double-buffered): 2 x (parity input 46.8 KB + 18.4 KB weights).
@@ -435,6 +435,14 @@ void launch_conv3x3(const Conv3x3Params& p, int stride, hipStream_t stream) {
         const int npix = nxb * nyb * p.B;
         const int ncb = (p.CT + NCT - 1) / NCT;
         dim3 grid((unsigned)(8 * ncb * ((npix + 7) / 8)));
-        conv3x3_kernel<2, YB, XW, 16, NCT, PW><<<grid, dim3(YB * XW * WAVE_SIZE), 0, stream>>>(p);
+        conv3x3_kernel<2, YB, XW, 16, NCT, PW, F16>
+            <<<grid, dim3(YB * XW * WAVE_SIZE), 0, stream>>>(p);
     }
+}
+
+void launch_conv3x3(const Conv3x3Params& p, int stride, int dtype, hipStream_t stream) {
+    if (dtype == DFA_F16)
+        launch_conv3x3_t<true>(p, stride, stream);
+    else
+        launch_conv3x3_t<false>(p, stride, stream);
 }

@@ -41,14 +41,14 @@ void launch_cfg_affine_step(const void* noise_u, const void* noise_c, const void
                             float g, float ca, float cb, int64_t total, int dtype,
                             hipStream_t stream);
 
-// ---- Implicit-GEMM 3x3 conv (bf16, NCHW, stride 1/2, pad 1) -----------------
+// ---- Implicit-GEMM 3x3 conv (bf16 or fp16, NCHW, stride 1/2, pad 1) -----------------
 // x: interior [B][Cin][H][W] (row-contiguous; x_sc = channel stride).
 // top/bot: optional single halo rows [B][Cin][1][W] (e.g. comm-buffer views);
 // null => zero padding at that border. Input row y_in=-1 reads top, y_in=H
 // reads bot. o: [B][Cout][Ho][Wo] contiguous output.
 // wp: weights prepacked in per-lane A-fragment order [9][KS][CT][64][8]
 // (cout = ct*32 + (lane&31), cin = ks*16 + (lane>>5)*8 + j), KS*16 and CT*32
-// zero-padded to multiples of 64/32. bias: bf16 [Cout] or null.
+// zero-padded to multiples of 64/32. bias: [Cout] or null.
 struct Conv3x3Params {
     const uint16_t* x;
     const uint16_t* top;
@@ -65,7 +65,8 @@ struct Conv3x3Params {
     int64_t t_sb, t_sc;
     int64_t b_sb, b_sc;
 };
-void launch_conv3x3(const Conv3x3Params& p, int stride, hipStream_t stream);
+// dtype: DFA_BF16 or DFA_F16 for x, halos, wp, bias, residual, bias2 and o alike
+void launch_conv3x3(const Conv3x3Params& p, int stride, int dtype, hipStream_t stream);
 
 // ---- fused CFG + DPM-Solver++(2M) step --------------------------------------
 // out = ca*x + cb*eps + cc*x0_prev (x0_prev may be null); x0_out = cx*x + ce*eps
@@ -73,14 +74,14 @@ void launch_cfg_dpm_step(const void* nu, const void* nc, const void* x, const vo
                          void* out, void* x0_out, float g, float ca, float cb, float cc,
                          float cx, float ce, int64_t total, int dtype, hipStream_t stream);
 
-// ---- fused (residual +) LayerNorm (bf16, C <= 2048, C % 8 == 0) -------------
+// ---- fused (residual +) LayerNorm (bf16 or fp16, C <= 2048, C % 8 == 0) -------------
 // y = LN(x [+ res]); when res != null and sum_out != null, x+res is also
 // written to sum_out (the transformer residual add fused away).
 void launch_layer_norm(const void* x, const void* res, void* y, void* sum_out,
                        const void* w, const void* b, float eps, int64_t rows, int C,
-                       hipStream_t stream);
+                       int dtype, hipStream_t stream);
 
-// ---- VAE mid-block attention (bf16, single head, head_dim 512) --------------
+// ---- VAE mid-block attention (bf16 or fp16, single head, head_dim 512) --------------
 // q/k/v/o: [B][L][512] row-contiguous (sb = batch stride in elements).
 struct VaeAttnParams {
     const uint16_t* q;
@@ -91,9 +92,9 @@ struct VaeAttnParams {
     int64_t L, sb;
     float scale;
 };
-void launch_vae_attention(const VaeAttnParams& p, hipStream_t stream);
+void launch_vae_attention(const VaeAttnParams& p, int dtype, hipStream_t stream);
 
-// ---- Flash attention (bf16, SD-family head dims) ----------------------------
+// ---- Flash attention (bf16 or fp16, SD-family head dims) ----------------------------
 // q: logical [B, H, Lq, 64]; k/v: logical [B, H, NC, LC, 64] (NC stale-KV
 // chunks of LC tokens; NC=1 for plain attention). All strides in ELEMENTS,
 // innermost head_dim contiguous. o: [B, Lq, H, 64] contiguous output.
@@ -110,11 +111,13 @@ struct FlashAttnParams {
     int64_t v_sb, v_sh, v_sc, v_sl;
     float scale;  // 1/sqrt(64)
 };
-void launch_flash_attention_d64(const FlashAttnParams& p, hipStream_t stream);
+// dtype: DFA_BF16 or DFA_F16, the element type of q/k/v/o (the caller rejects
+// DFA_F32); a template axis of the kernel, the parameter block is the same.
+void launch_flash_attention_d64(const FlashAttnParams& p, int dtype, hipStream_t stream);
 
 // LSE / split-KV mode of the same kernel. lse: fp32 [S, B, H, Lq], the natural
 // log of each row's sum of exp(scale * q.k) over the split's KV slice (-inf
-// for an empty slice). o_part == null (S == 1 only): bf16 O goes to `o` as in
+// for an empty slice). o_part == null (S == 1 only): 16-bit O goes to `o` as in
 // the plain mode. o_part != null: split s writes its normalised partial
 // output as fp32 into o_part [S, B, Lq, H, Dh]; `o` is not touched.
 struct FlashAttnLseParams : FlashAttnParams {
@@ -124,13 +127,14 @@ struct FlashAttnLseParams : FlashAttnParams {
 // S the launcher uses for a request of `splits`: clamped to [1, ceil(Lkv/128)]
 // (splits are tile-aligned and never empty).
 int flash_attention_num_splits(int64_t lkv, int splits);
-void launch_flash_attention_lse(const FlashAttnLseParams& p, int splits, hipStream_t stream);
+void launch_flash_attention_lse(const FlashAttnLseParams& p, int splits, int dtype,
+                                hipStream_t stream);
 
 // ---- merge of attention partials ----------------------------------------------
 // out[b,q,h,:] = sum_s w_s o_parts[s,b,q,h,:] / sum_s w_s, w_s = exp(lse_s - max_s lse_s);
 // lse = max + ln sum_s w_s (optional). A part with lse = -inf has weight 0; all
 // parts -inf gives zeros and lse = -inf. o_parts fp32 [S, B, Lq, H, Dh],
-// lse_parts fp32 [S, B, H, Lq], out [B, Lq, H, Dh] bf16 or fp32, Dh % 8 == 0.
+// lse_parts fp32 [S, B, H, Lq], out [B, Lq, H, Dh] bf16, fp16 or fp32, Dh % 8 == 0.
 struct MergeAttnParams {
     const float* o_parts;
     const float* lse_parts;
@@ -138,6 +142,6 @@ struct MergeAttnParams {
     float* lse;  // [B, H, Lq] or null
     int S, B, H, Dh;
     int64_t Lq;
-    bool out_bf16;
+    int out_dtype;  // DfaDtype of `out`
 };
 void launch_merge_attention(const MergeAttnParams& p, hipStream_t stream);

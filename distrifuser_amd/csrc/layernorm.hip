@@ -1,4 +1,4 @@
-// Fused (residual-add +) LayerNorm, gfx950, bf16 (SURVEY hotlist item:
+// Fused (residual-add +) LayerNorm, gfx950, bf16 or fp16 (SURVEY hotlist item:
 // at::native vectorized_layer_norm + the transformer residual adds were
 // ~4-5% of the 3840^2 step, profiles/rocprof_3840_r01_v2.md rows 6/9/10).
 //
@@ -14,7 +14,7 @@ namespace {
 
 constexpr int WPB = 4;  // waves (rows) per block
 
-template <int VPT>  // 8-element vectors per lane
+template <int VPT, bool F16>  // 8-element vectors per lane; fp16 or bf16 elements
 __global__ __launch_bounds__(WPB* WAVE_SIZE) void ln_kernel(
     const uint16_t* __restrict__ x, const uint16_t* __restrict__ res,
     uint16_t* __restrict__ y, uint16_t* __restrict__ sum_out,
@@ -38,8 +38,8 @@ __global__ __launch_bounds__(WPB* WAVE_SIZE) void ln_kernel(
             if (rp) rv = *reinterpret_cast<const short8*>(rp + d0);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                float f = to_f32(__builtin_bit_cast(bf16_t, (short)xv[j]));
-                if (rp) f += to_f32(__builtin_bit_cast(bf16_t, (short)rv[j]));
+                float f = b16_to_f32<F16>((uint16_t)xv[j]);
+                if (rp) f += b16_to_f32<F16>((uint16_t)rv[j]);
                 v[k][j] = f;
                 s += f;
                 ss += f * f;
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(WPB* WAVE_SIZE) void ln_kernel(
                 uint16_t sv[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j)
-                    sv[j] = __builtin_bit_cast(uint16_t, __float2bfloat16(v[k][j]));
+                    sv[j] = f32_to_b16<F16>(v[k][j]);
                 *reinterpret_cast<uint4*>(sum_out + row * C + d0) =
                     *reinterpret_cast<const uint4*>(sv);
             }
@@ -73,10 +73,9 @@ __global__ __launch_bounds__(WPB* WAVE_SIZE) void ln_kernel(
             uint16_t out[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const float wf = to_f32(__builtin_bit_cast(bf16_t, (short)wv[j]));
-                const float bf = to_f32(__builtin_bit_cast(bf16_t, (short)bv[j]));
-                out[j] = __builtin_bit_cast(
-                    uint16_t, __float2bfloat16((v[k][j] - mean) * inv * wf + bf));
+                const float wf = b16_to_f32<F16>((uint16_t)wv[j]);
+                const float bf = b16_to_f32<F16>((uint16_t)bv[j]);
+                out[j] = f32_to_b16<F16>((v[k][j] - mean) * inv * wf + bf);
             }
             *reinterpret_cast<uint4*>(yp + d0) = *reinterpret_cast<const uint4*>(out);
         }
@@ -85,9 +84,10 @@ __global__ __launch_bounds__(WPB* WAVE_SIZE) void ln_kernel(
 
 }  // namespace
 
-void launch_layer_norm(const void* x, const void* res, void* y, void* sum_out,
-                       const void* w, const void* b, float eps, int64_t rows, int C,
-                       hipStream_t stream) {
+template <bool F16>
+static void launch_layer_norm_t(const void* x, const void* res, void* y, void* sum_out,
+                                const void* w, const void* b, float eps, int64_t rows, int C,
+                                hipStream_t stream) {
     dim3 grid((unsigned)((rows + WPB - 1) / WPB));
     dim3 block(WPB * WAVE_SIZE);
     const auto* xp = reinterpret_cast<const uint16_t*>(x);
@@ -97,11 +97,20 @@ void launch_layer_norm(const void* x, const void* res, void* y, void* sum_out,
     const auto* wp = reinterpret_cast<const uint16_t*>(w);
     const auto* bp = reinterpret_cast<const uint16_t*>(b);
     if (C <= 512)
-        ln_kernel<1><<<grid, block, 0, stream>>>(xp, rp, yp, sp, wp, bp, eps, rows, C);
+        ln_kernel<1, F16><<<grid, block, 0, stream>>>(xp, rp, yp, sp, wp, bp, eps, rows, C);
     else if (C <= 1024)
-        ln_kernel<2><<<grid, block, 0, stream>>>(xp, rp, yp, sp, wp, bp, eps, rows, C);
+        ln_kernel<2, F16><<<grid, block, 0, stream>>>(xp, rp, yp, sp, wp, bp, eps, rows, C);
     else if (C <= 1536)
-        ln_kernel<3><<<grid, block, 0, stream>>>(xp, rp, yp, sp, wp, bp, eps, rows, C);
+        ln_kernel<3, F16><<<grid, block, 0, stream>>>(xp, rp, yp, sp, wp, bp, eps, rows, C);
     else
-        ln_kernel<4><<<grid, block, 0, stream>>>(xp, rp, yp, sp, wp, bp, eps, rows, C);
+        ln_kernel<4, F16><<<grid, block, 0, stream>>>(xp, rp, yp, sp, wp, bp, eps, rows, C);
+}
+
+void launch_layer_norm(const void* x, const void* res, void* y, void* sum_out,
+                       const void* w, const void* b, float eps, int64_t rows, int C,
+                       int dtype, hipStream_t stream) {
+    if (dtype == DFA_F16)
+        launch_layer_norm_t<true>(x, res, y, sum_out, w, b, eps, rows, C, stream);
+    else
+        launch_layer_norm_t<false>(x, res, y, sum_out, w, b, eps, rows, C, stream);
 }

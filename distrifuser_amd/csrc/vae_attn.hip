@@ -1,4 +1,4 @@
-// VAE mid-block attention, gfx950, bf16: SINGLE head with head_dim 512
+// VAE mid-block attention, gfx950, bf16 or fp16: SINGLE head with head_dim 512
 // (SURVEY §2.4a K12 — the SD VAE decoder's 512-channel attention).
 //
 // d=512 cannot ride the d64 flash kernel: per-lane O accumulators would be
@@ -49,10 +49,12 @@ __device__ __forceinline__ short8 lds_frag_b64x2(const char* addr) {
     return __builtin_bit_cast(short8, v);
 }
 
+// F16: q/k/v/o, the P tile and the O staging are IEEE fp16 instead of bf16
+template <bool F16>
 __global__ __launch_bounds__(NW * WAVE_SIZE) void vae_attn_kernel(VaeAttnParams p) {
     __shared__ char k_lds[KVB * K_ROW];          // [t][d]; reused as o_lds
     __shared__ char vt_lds[C * VT_ROW];          // [d][t]
-    __shared__ char p_lds[QT * P_ROW];           // [q][t] bf16
+    __shared__ char p_lds[QT * P_ROW];           // [q][t] bf16 / fp16
     // split-K: waves ds_add_f32 their partials into ONE tile (4 KB; the
     // per-wave-slab version cost 16 KB and dropped occupancy to 1 block/CU)
     __shared__ float s_red[KVB][QT];
@@ -124,7 +126,7 @@ __global__ __launch_bounds__(NW * WAVE_SIZE) void vae_attn_kernel(VaeAttnParams 
                 uint4 raw = {0, 0, 0, 0};
                 if (tg < p.L)
                     raw = *reinterpret_cast<const uint4*>(vb + tg * C + d0);
-                const uint4 tr = transpose8x8_bf16(raw, lane);
+                const uint4 tr = transpose8x8_b16(raw, lane);
                 const int d = (db * 8 + gw) * 8 + gr;
                 char* dst = &vt_lds[d * VT_ROW + (tw * 8) * 2];
                 *reinterpret_cast<uint2*>(dst) = uint2{tr.x, tr.y};
@@ -140,7 +142,7 @@ __global__ __launch_bounds__(NW * WAVE_SIZE) void vae_attn_kernel(VaeAttnParams 
         for (int ks = 0; ks < KS; ++ks) {
             const short8 kf = lds_frag_b64x2(
                 &k_lds[lo * K_ROW + (wave * DSL + ks * 16 + hi * 8) * 2]);
-            s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], s, 0, 0, 0);
+            s = mfma_32x32x16<F16>(kf, qf[ks], s);
         }
         __builtin_amdgcn_s_setprio(0);
         // lane holds S^T rows t = (r&3)+8*(r>>2)+4*hi for q col lo
@@ -179,7 +181,7 @@ __global__ __launch_bounds__(NW * WAVE_SIZE) void vae_attn_kernel(VaeAttnParams 
             for (int j = 0; j < 4; ++j) {
                 const float pe = __builtin_amdgcn_exp2f(__builtin_fmaf(sv[j], scale2, -msc));
                 tsum += pe;
-                reinterpret_cast<bf16_t*>(&p_lds[q * P_ROW])[t0l + j] = __float2bfloat16(pe);
+                reinterpret_cast<uint16_t*>(&p_lds[q * P_ROW])[t0l + j] = f32_to_b16<F16>(pe);
             }
             tsum += __shfl_xor(tsum, 1, WAVE_SIZE);
             tsum += __shfl_xor(tsum, 2, WAVE_SIZE);
@@ -213,7 +215,7 @@ __global__ __launch_bounds__(NW * WAVE_SIZE) void vae_attn_kernel(VaeAttnParams 
                     const short8 pf = lds_frag_b64x2(
                         &p_lds[lo * P_ROW + (kt * 16 + hi * 8) * 2]);
                     // A = V^T rows d, B = P^T cols q -> O^T[d][q]
-                    ot[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, ot[dt], 0, 0, 0);
+                    ot[dt] = mfma_32x32x16<F16>(vf, pf, ot[dt]);
                 }
             }
             __builtin_amdgcn_s_setprio(0);
@@ -230,8 +232,8 @@ __global__ __launch_bounds__(NW * WAVE_SIZE) void vae_attn_kernel(VaeAttnParams 
             for (int r = 0; r < 16; ++r) {
                 const int d = wave * DSL + dt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
                 const float inv = l_lds[lo] > 0.f ? 1.f / l_lds[lo] : 0.f;
-                reinterpret_cast<bf16_t*>(&o_lds[lo * O_ROW])[d] =
-                    __float2bfloat16(ot[dt][r] * inv);
+                reinterpret_cast<uint16_t*>(&o_lds[lo * O_ROW])[d] =
+                    f32_to_b16<F16>(ot[dt][r] * inv);
             }
     }
     __syncthreads();
@@ -255,7 +257,10 @@ __global__ __launch_bounds__(NW * WAVE_SIZE) void vae_attn_kernel(VaeAttnParams 
 
 }  // namespace
 
-void launch_vae_attention(const VaeAttnParams& p, hipStream_t stream) {
+void launch_vae_attention(const VaeAttnParams& p, int dtype, hipStream_t stream) {
     dim3 grid((unsigned)((p.L + QT - 1) / QT), (unsigned)p.B);
-    vae_attn_kernel<<<grid, dim3(NW * WAVE_SIZE), 0, stream>>>(p);
+    if (dtype == DFA_F16)
+        vae_attn_kernel<true><<<grid, dim3(NW * WAVE_SIZE), 0, stream>>>(p);
+    else
+        vae_attn_kernel<false><<<grid, dim3(NW * WAVE_SIZE), 0, stream>>>(p);
 }

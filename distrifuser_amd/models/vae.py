@@ -75,7 +75,11 @@ def _chunked_single_head_attention(
     # GPU: bf16 GEMMs (hipBLASLt) with fp32 softmax — at 230k tokens the
     # score GEMM is ~5e16 FLOP and fp32 (vector-ALU only on CDNA4, no fp32
     # MFMA) would take minutes; CPU keeps fp32 for the test oracle.
-    mm_dtype = torch.bfloat16 if q.is_cuda else torch.float32
+    # An fp16 input keeps its own type: same GEMM rate, three more mantissa bits.
+    if not q.is_cuda:
+        mm_dtype = torch.float32
+    else:
+        mm_dtype = torch.float16 if q.dtype == torch.float16 else torch.bfloat16
     qs = (q.float() * scale).to(mm_dtype)
     ks = k.to(mm_dtype)
     vs = v.to(mm_dtype)
@@ -105,7 +109,7 @@ class VAEAttention(nn.Module):
                                 self.group_norm.bias, self.group_norm.eps, silu=False)
         x = x.permute(0, 2, 3, 1).reshape(b, h * w, c)
         q, k, v = self.to_q(x), self.to_k(x), self.to_v(x)
-        if x.is_cuda and c == 512 and q.dtype == torch.bfloat16:
+        if x.is_cuda and c == 512 and q.dtype in (torch.bfloat16, torch.float16):
             out = ops.vae_attention(q, k, v)  # split-D HIP kernel
         elif x.is_cuda and c <= 256:
             out = ops.flash_attention(q[:, None], k[:, None], v[:, None])[:, 0]

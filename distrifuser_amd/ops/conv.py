@@ -16,14 +16,21 @@ from . import eager
 from .dispatch import _use_hip, hip_ext
 
 
-def pack_conv3x3_weight(weight: torch.Tensor) -> torch.Tensor:
-    """[Cout, Cin, 3, 3] -> [9, KS, CT, 64, 8] bf16 in A-fragment order.
+_CONV_DTYPES = (torch.bfloat16, torch.float16)
 
-    Fragment map (mfma_f32_32x32x16_bf16 A operand): lane l holds
-    cout = ct*32 + (l&31), cin = ks*16 + (l>>5)*8 + j for j in 0..7.
-    Cin is zero-padded to a multiple of 64 (the kernel's largest staged
+
+def pack_conv3x3_weight(weight: torch.Tensor, dtype: torch.dtype | None = None) -> torch.Tensor:
+    """[Cout, Cin, 3, 3] -> [9, KS, CT, 64, 8] in A-fragment order, as bf16
+    (dtype None, the default) or fp16 (dtype=torch.float16).
+
+    Fragment map (mfma_f32_32x32x16_bf16 / _f16 A operand, the same for both):
+    lane l holds cout = ct*32 + (l&31), cin = ks*16 + (l>>5)*8 + j for j in
+    0..7. Cin is zero-padded to a multiple of 64 (the kernel's largest staged
     cin tile), Cout to a multiple of 32.
     """
+    dtype = torch.bfloat16 if dtype is None else dtype
+    if dtype not in _CONV_DTYPES:
+        raise ValueError(f"pack_conv3x3_weight: dtype must be bf16 or fp16, got {dtype}")
     cout, cin, kh, kw = weight.shape
     assert kh == 3 and kw == 3, "pack_conv3x3_weight is 3x3 only"
     cin_p = (cin + 63) // 64 * 64
@@ -34,12 +41,12 @@ def pack_conv3x3_weight(weight: torch.Tensor) -> torch.Tensor:
     wp = wp.permute(2, 1, 0)              # [9][cin_p][cout_p]
     wp = wp.reshape(9, ks, 2, 8, ct, 32)  # cin = ks*16 + hi*8 + j
     wp = wp.permute(0, 1, 4, 2, 5, 3)     # [9][ks][ct][hi][cout%32][j]
-    return wp.reshape(9, ks, ct, 64, 8).contiguous().to(torch.bfloat16)
+    return wp.reshape(9, ks, ct, 64, 8).contiguous().to(dtype)
 
 
 def _hip_conv_ok(x: torch.Tensor, stride: int) -> bool:
     return (
-        x.dtype == torch.bfloat16
+        x.dtype in _CONV_DTYPES
         and stride in (1, 2)
         and x.stride(-1) == 1
         and x.stride(-2) == x.shape[-1]
@@ -95,7 +102,7 @@ class NativeConv2d(nn.Conv2d):
             and self.stride[0] in (1, 2)
             and self.dilation == (1, 1)
             and self.groups == 1
-            and x.dtype == torch.bfloat16
+            and x.dtype in _CONV_DTYPES
         )
 
     def packed_weight(self) -> torch.Tensor:
@@ -103,7 +110,9 @@ class NativeConv2d(nn.Conv2d):
         key = (w._version, w.data_ptr(), w.dtype, w.device)
         if self._wp is None or self._wp_key != key:
             with torch.no_grad():
-                self._wp = pack_conv3x3_weight(w.detach())
+                # fp16 weights pack as fp16; anything else as bf16, as ever
+                self._wp = pack_conv3x3_weight(
+                    w.detach(), torch.float16 if w.dtype == torch.float16 else None)
             self._wp_key = key
         return self._wp
 

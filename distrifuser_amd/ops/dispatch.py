@@ -53,12 +53,15 @@ def _use_hip(x: torch.Tensor) -> bool:
 
 
 _FLASH_HEAD_DIMS = (40, 64, 80, 96, 128, 160)  # SD-family head dims
+_KERNEL_DTYPES = (torch.bfloat16, torch.float16)  # element types of the MFMA kernels and LN
 
 
 def _flash_ok(q: torch.Tensor, *kv: torch.Tensor) -> bool:
-    if q.dtype != torch.bfloat16 or q.shape[-1] not in _FLASH_HEAD_DIMS:
+    if q.dtype not in _KERNEL_DTYPES or q.shape[-1] not in _FLASH_HEAD_DIMS:
         return False
     for t in (q, *kv):
+        if t.dtype != q.dtype:
+            return False
         if t.stride(-1) != 1:
             return False
         if any(s % 8 != 0 for s in t.stride()[:-1]):
@@ -97,7 +100,7 @@ def flash_attention(
             return hip_ext().flash_attention(q, k, v)
         res = hip_ext().flash_attention_ext(q, k, v, kv_splits, return_lse)
         return (res[0], res[1]) if return_lse else res[0]
-    # CPU, or non-bf16 / odd head-dims on GPU (PyTorch's SDPA, rocm AOTriton path)
+    # CPU, or fp32 / odd head-dims on GPU (PyTorch's SDPA, rocm AOTriton path)
     if return_lse:
         return eager.flash_attention_lse(q, k, v)
     return eager.flash_attention(q, k, v)
@@ -147,7 +150,7 @@ def merge_attention(
     lse_parts: [S, B, H, Lq]. Returns out [B, Lq, H, D] in out_dtype (default:
     the parts' dtype), with return_lse also the merged fp32 lse [B, H, Lq].
     Parts with lse = -inf weigh 0; all -inf gives zeros and lse = -inf. The
-    gfx950 kernel takes contiguous fp32 parts and writes bf16 or fp32;
+    gfx950 kernel takes contiguous fp32 parts and writes bf16, fp16 or fp32;
     anything else runs the eager reference.
     """
     dt = o_parts.dtype if out_dtype is None else out_dtype
@@ -155,13 +158,13 @@ def merge_attention(
         _use_hip(o_parts)
         and o_parts.dtype == torch.float32
         and lse_parts.dtype == torch.float32
-        and dt in (torch.bfloat16, torch.float32)
+        and dt in (torch.bfloat16, torch.float16, torch.float32)
         and o_parts.dim() == 5
         and o_parts.shape[-1] % 8 == 0
         and o_parts.is_contiguous()
         and lse_parts.is_contiguous()
     ):
-        out, lse = hip_ext().merge_attention(o_parts, lse_parts, dt == torch.bfloat16)
+        out, lse = hip_ext().merge_attention(o_parts, lse_parts, dt == torch.bfloat16, dt)
     else:
         out, lse = eager.merge_attention(o_parts, lse_parts, dt)
     return (out, lse) if return_lse else out
@@ -257,14 +260,14 @@ def group_norm_silu(x, num_groups, weight, bias, eps, silu=True):
 
 
 def layer_norm(x, weight, bias, eps):
-    if _use_hip(x) and x.dtype == torch.bfloat16 and x.shape[-1] % 8 == 0 and x.shape[-1] <= 2048:
+    if _use_hip(x) and x.dtype in _KERNEL_DTYPES and x.shape[-1] % 8 == 0 and x.shape[-1] <= 2048:
         return hip_ext().layer_norm(x, weight, bias, eps)
     return eager.layer_norm(x, weight, bias, eps)
 
 
 def add_layer_norm(x, res, weight, bias, eps):
     """(x + res, LN(x + res)) in one kernel on GPU."""
-    if _use_hip(x) and x.dtype == torch.bfloat16 and x.shape[-1] % 8 == 0 and x.shape[-1] <= 2048:
+    if _use_hip(x) and x.dtype in _KERNEL_DTYPES and x.shape[-1] % 8 == 0 and x.shape[-1] <= 2048:
         s, y = hip_ext().add_layer_norm(x, res, weight, bias, eps)
         return s, y
     return eager.add_layer_norm(x, res, weight, bias, eps)
@@ -272,7 +275,7 @@ def add_layer_norm(x, res, weight, bias, eps):
 
 def vae_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
     """Single-head d=512 attention, q/k/v [B, L, 512] (VAE mid block)."""
-    if _use_hip(q) and q.dtype == torch.bfloat16 and q.shape[-1] == 512:
+    if _use_hip(q) and q.dtype in _KERNEL_DTYPES and q.shape[-1] == 512:
         return hip_ext().vae_attention(q, k, v)
     return eager.vae_attention(q, k, v)
 

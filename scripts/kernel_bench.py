@@ -1,7 +1,9 @@
 """Quick on-box kernel A/B: our gfx950 kernels vs the PyTorch-ROCm baselines.
 
 Run on an MI355X: python scripts/kernel_bench.py > gpurun_out/kernel_bench.json
-(--splitkv-only: just the split-KV attention sweep)
+(--splitkv-only: just the split-KV attention sweep; --dtype {bf16,fp16}: the
+element type of the attention, conv, LayerNorm and VAE-attention rows, default
+bf16 — fp16 rows carry "dtype": "fp16")
 """
 
 import os
@@ -80,6 +82,11 @@ def main():
 
     dev = "cuda:0"
     results = []
+    argv = sys.argv[1:]
+    dtype_name = argv[argv.index("--dtype") + 1] if "--dtype" in argv else "bf16"
+    assert dtype_name in ("bf16", "fp16"), "--dtype takes bf16 or fp16"
+    dt = torch.float16 if dtype_name == "fp16" else torch.bfloat16
+    tag = {"dtype": "fp16"} if dtype_name == "fp16" else {}  # bf16 rows: as ever
 
     if "--splitkv-only" in sys.argv[1:]:
         splitkv_sweep(results)
@@ -91,13 +98,14 @@ def main():
     #   (heads, L): 1024^2 -> (10, 4096) and (20, 1024)
     #   3840^2 -> (10, 57600) and (20, 14400)
     for h, l in [(20, 1024), (10, 4096), (20, 14400), (10, 57600)]:
-        q = torch.randn(1, h, l, 64, device=dev, dtype=torch.bfloat16)
-        k = torch.randn(1, h, l, 64, device=dev, dtype=torch.bfloat16)
-        v = torch.randn(1, h, l, 64, device=dev, dtype=torch.bfloat16)
+        q = torch.randn(1, h, l, 64, device=dev, dtype=dt)
+        k = torch.randn(1, h, l, 64, device=dev, dtype=dt)
+        v = torch.randn(1, h, l, 64, device=dev, dtype=dt)
         ms_ours = timeit(lambda: ops.hip_ext().flash_attention(q, k, v))
         ms_sdpa = timeit(lambda: F.scaled_dot_product_attention(q, k, v))
         flops = 4.0 * l * l * 64 * h
         results.append({
+            **tag,
             "op": "flash_attention", "heads": h, "L": l,
             "ms_ours": ms_ours, "ms_sdpa": ms_sdpa,
             "tflops_ours": flops / ms_ours / 1e9,
@@ -109,9 +117,9 @@ def main():
     for h, lq, n in [(10, 7200, 8), (20, 3600, 4)]:
         lkv = lq * n
         inner = h * 64
-        q = torch.randn(1, h, lq, 64, device=dev, dtype=torch.bfloat16)
+        q = torch.randn(1, h, lq, 64, device=dev, dtype=dt)
         slot = lq * 2 * inner
-        buf = torch.randn(n, slot + 64, device=dev, dtype=torch.bfloat16)
+        buf = torch.randn(n, slot + 64, device=dev, dtype=dt)
         kv = buf[:, :slot].view(n, 1, lq, 2 * inner)
         k5 = kv[..., :inner].unflatten(-1, (h, 64)).permute(1, 3, 0, 2, 4)
         v5 = kv[..., inner:].unflatten(-1, (h, 64)).permute(1, 3, 0, 2, 4)
@@ -122,6 +130,7 @@ def main():
         ms_sdpa = timeit(lambda: F.scaled_dot_product_attention(q, kcat, vcat))
         flops = 4.0 * lq * lkv * 64 * h
         results.append({
+            **tag,
             "op": "flash_attention_stale_chunked", "heads": h, "Lq": lq, "Lkv": lkv,
             "n_chunks": n, "ms_ours": ms_ours, "ms_sdpa_precat": ms_sdpa,
             "tflops_ours": flops / ms_ours / 1e9,
@@ -144,15 +153,16 @@ def main():
         (960, 320, 480, 480, 1),
     ]
     for cin, cout, h, w, s in conv_shapes:
-        x = torch.randn(2, cin, h, w, device=dev, dtype=torch.bfloat16) * 0.5
-        wt = torch.randn(cout, cin, 3, 3, device=dev, dtype=torch.bfloat16) * (cin * 9) ** -0.5
-        bias = torch.randn(cout, device=dev, dtype=torch.bfloat16)
-        packed = ops.pack_conv3x3_weight(wt)
+        x = torch.randn(2, cin, h, w, device=dev, dtype=dt) * 0.5
+        wt = torch.randn(cout, cin, 3, 3, device=dev, dtype=dt) * (cin * 9) ** -0.5
+        bias = torch.randn(cout, device=dev, dtype=dt)
+        packed = ops.pack_conv3x3_weight(wt, dt)
         ms_ours = timeit(lambda: ops.conv3x3_halo(x, wt, bias, s, packed=packed))
         ms_ref = timeit(lambda: F.conv2d(x, wt, bias, stride=s, padding=1))
         ho, wo = (h - 1) // s + 1, (w - 1) // s + 1
         flops = 2.0 * 2 * cout * ho * wo * cin * 9
         results.append({
+            **tag,
             "op": "conv3x3", "cin": cin, "cout": cout, "h": h, "w": w, "stride": s,
             "ms_ours": ms_ours, "ms_miopen": ms_ref,
             "tflops_ours": flops / ms_ours / 1e9,
@@ -193,10 +203,10 @@ def main():
 
     # ---- fused (residual+)LayerNorm at SDXL transformer shapes ----
     for rows, c in [(57600, 640), (14400, 1280), (4096, 640)]:
-        x = torch.randn(1, rows, c, device=dev, dtype=torch.bfloat16)
-        r = torch.randn(1, rows, c, device=dev, dtype=torch.bfloat16)
-        w = torch.randn(c, device=dev, dtype=torch.bfloat16)
-        b = torch.randn(c, device=dev, dtype=torch.bfloat16)
+        x = torch.randn(1, rows, c, device=dev, dtype=dt)
+        r = torch.randn(1, rows, c, device=dev, dtype=dt)
+        w = torch.randn(c, device=dev, dtype=dt)
+        b = torch.randn(c, device=dev, dtype=dt)
         ms_ours = timeit(lambda: ops.hip_ext().add_layer_norm(x, r, w, b, 1e-5))
         def ref():
             s2 = x + r
@@ -204,6 +214,7 @@ def main():
         ms_ref = timeit(ref)
         gb = x.numel() * 2 * 4 / 1e9  # 2 reads + 2 writes
         results.append({
+            **tag,
             "op": "add_layer_norm", "rows": rows, "C": c,
             "ms_ours": ms_ours, "ms_torch": ms_ref,
             "tbps_ours": gb / ms_ours, "tbps_torch": gb / ms_ref,
@@ -212,12 +223,13 @@ def main():
 
     # ---- VAE 512-dim single-head mid attention ----
     for l in (4096, 16384):
-        q = torch.randn(1, l, 512, device=dev, dtype=torch.bfloat16)
-        k = torch.randn(1, l, 512, device=dev, dtype=torch.bfloat16)
-        v = torch.randn(1, l, 512, device=dev, dtype=torch.bfloat16)
+        q = torch.randn(1, l, 512, device=dev, dtype=dt)
+        k = torch.randn(1, l, 512, device=dev, dtype=dt)
+        v = torch.randn(1, l, 512, device=dev, dtype=dt)
         ms_ours = timeit(lambda: ops.hip_ext().vae_attention(q, k, v), iters=5, warmup=2)
         flops = 4.0 * l * l * 512
         results.append({
+            **tag,
             "op": "vae_attention", "L": l, "ms_ours": ms_ours,
             "tflops_ours": flops / ms_ours / 1e9,
         })
