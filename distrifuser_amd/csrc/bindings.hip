@@ -324,7 +324,7 @@ at::Tensor conv3x3(const at::Tensor& x, const at::Tensor& wp,
                    const c10::optional<at::Tensor>& bias, int64_t cout, int64_t stride,
                    const c10::optional<at::Tensor>& top, const c10::optional<at::Tensor>& bot,
                    const c10::optional<at::Tensor>& residual,
-                   const c10::optional<at::Tensor>& bias2) {
+                   const c10::optional<at::Tensor>& bias2, int64_t pad_lo) {
     TORCH_CHECK(x.is_cuda() && x.dim() == 4 && is_b16(x),
                 "x must be CUDA bf16 or fp16 [B,Cin,H,W]");
     const auto dt = x.scalar_type();
@@ -336,7 +336,15 @@ at::Tensor conv3x3(const at::Tensor& x, const at::Tensor& wp,
                 wp.scalar_type());
     TORCH_CHECK(stride == 1 || stride == 2);
     const int B = (int)x.size(0), Cin = (int)x.size(1), H = (int)x.size(2), W = (int)x.size(3);
-    const int Ho = (H - 1) / (int)stride + 1, Wo = (W - 1) / (int)stride + 1;
+    TORCH_CHECK(pad_lo == 0 || pad_lo == 1, "conv3x3: pad_lo must be 0 or 1, got ", pad_lo);
+    if (pad_lo == 0) {
+        // bottom/right-only padding (AutoencoderKL downsample)
+        TORCH_CHECK(stride == 2, "conv3x3: pad_lo=0 needs stride 2, got ", stride);
+        TORCH_CHECK(!top.has_value(), "conv3x3: pad_lo=0 takes no top halo row");
+        TORCH_CHECK(H >= 2 && W >= 2, "conv3x3: pad_lo=0 needs H, W >= 2, got ", H, "x", W);
+    }
+    const int Ho = pad_lo ? (H - 1) / (int)stride + 1 : (H - 2) / 2 + 1;
+    const int Wo = pad_lo ? (W - 1) / (int)stride + 1 : (W - 2) / 2 + 1;
 
     Conv3x3Params p{};
     p.x = reinterpret_cast<const uint16_t*>(x.data_ptr());
@@ -350,6 +358,7 @@ at::Tensor conv3x3(const at::Tensor& x, const at::Tensor& wp,
     p.Wo = Wo;
     p.KS = (int)wp.size(1);
     p.CT = (int)wp.size(2);
+    p.pad_lo = (int)pad_lo;
     TORCH_CHECK(p.KS * 16 >= Cin && p.CT * 32 >= cout, "packed weight too small");
     p.x_sb = x.stride(0);
     p.x_sc = x.stride(1);
@@ -542,7 +551,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("add_layer_norm", &add_layer_norm, "bf16/fp16 fused residual-add + LayerNorm -> (sum, y)");
     m.def("vae_attention", &vae_attention, "bf16/fp16 single-head d=512 VAE mid attention");
     m.def("conv3x3", &conv3x3,
-          "bf16/fp16 implicit-GEMM 3x3 conv, stride 1/2, in-place halo rows");
+          "bf16/fp16 implicit-GEMM 3x3 conv, stride 1/2, in-place halo rows; pad_lo=0 "
+          "(stride 2) pads bottom/right only",
+          pybind11::arg("x"), pybind11::arg("wp"), pybind11::arg("bias"), pybind11::arg("cout"), pybind11::arg("stride"),
+          pybind11::arg("top"), pybind11::arg("bot"), pybind11::arg("residual"), pybind11::arg("bias2"),
+          pybind11::arg("pad_lo") = 1);
     m.def("mfma_probe", &mfma_probe, "dump mfma_f32_16x16x32_bf16 fragment mapping");
     m.def("mfma_probe32", &mfma_probe32, "dump mfma_f32_32x32x16_bf16 fragment mapping");
 }

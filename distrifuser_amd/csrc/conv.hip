@@ -69,8 +69,17 @@ __device__ __forceinline__ int32x4_ck make_srsrc(const void* base, uint32_t byte
 //   load bursts are issued in arrays before the transpose+write pass.
 // F16: every 16-bit tensor is IEEE fp16 instead of bf16 (the MFMA and the
 // epilogue conversions change type; staging moves 16-bit words either way).
-template <int S, int YB, int XW, int CIN_T, int NCT, int PW, bool F16 = false>
+// PL: low-side padding. 1 is the symmetric pad-1 conv. 0 (stride 2 only) is
+// the AutoencoderKL downsample, padded on the bottom and right alone: output
+// (y, x) reads rows 2y..2y+2 and columns 2x..2x+2, row H is bot or zero and
+// column W is zero. The staged tile keeps its layout (xi >= 1 are the same
+// 8-aligned windows from xb0*S); its row origin moves down to yb0*S, fragment
+// reads shift one column right (xi = 2x + dx + 1), and the scalar column pass
+// stages xi = XIN (x = xb0*S + 2*XB, plane 1 row XB) instead of the left halo
+// xi = 0, which this mode never reads.
+template <int S, int YB, int XW, int CIN_T, int NCT, int PW, bool F16 = false, int PL = 1>
 __global__ __launch_bounds__(YB * XW * WAVE_SIZE) void conv3x3_kernel(Conv3x3Params p) {
+    static_assert(PL == 1 || (PL == 0 && S == 2), "pad_lo = 0 is the stride-2 downsample only");
     constexpr int NW = YB * XW;
     constexpr int XB = XW * 32 * PW;
     constexpr int YIN = (YB - 1) * S + 3;          // staged input rows
@@ -157,7 +166,7 @@ __global__ __launch_bounds__(YB * XW * WAVE_SIZE) void conv3x3_kernel(Conv3x3Par
         const int xs = slab % NXS;
         const int cg = (slab / NXS) % CG;
         const int ry = slab / (NXS * CG);
-        const int y_in = yb0 * S - 1 + ry;
+        const int y_in = yb0 * S - PL + ry;
         const int xw = xs * 8 + gw;
         const int x_in0 = xb0 * S + xw * 8;
         if (y_in >= 0 && y_in < p.H) interior_mask |= 1u << sit;
@@ -244,7 +253,7 @@ __global__ __launch_bounds__(YB * XW * WAVE_SIZE) void conv3x3_kernel(Conv3x3Par
                     // W % 8 != 0: rows are not 16 B aligned; guarded scalar
                     // loads (correctness path, non-SD shapes)
                     const int cin = cin0 + cg * 8 + gr;
-                    const int y_in = yb0 * S - 1 + ry;
+                    const int y_in = yb0 * S - PL + ry;
                     if (cin < p.Cin) {
                         const uint16_t* rp = xin + (int64_t)cin * p.x_sc + (int64_t)y_in * p.W;
                         uint16_t vals[8];
@@ -256,7 +265,7 @@ __global__ __launch_bounds__(YB * XW * WAVE_SIZE) void conv3x3_kernel(Conv3x3Par
                 }
             } else {
                 // halo / zero rows (block at a patch boundary): rare
-                const int y_in = yb0 * S - 1 + ry;
+                const int y_in = yb0 * S - PL + ry;
                 const uint16_t* src = nullptr;
                 int64_t sc = 0;
                 if (y_in == -1 && top) {
@@ -286,15 +295,19 @@ __global__ __launch_bounds__(YB * XW * WAVE_SIZE) void conv3x3_kernel(Conv3x3Par
                 *reinterpret_cast<uint2*>(dst + 8) = uint2{tr.z, tr.w};
             }
         }
-        // left halo column xi = 0 (x_in = xb0*S - 1): scalar, tiny
+        // left halo column xi = 0 (x_in = xb0*S - 1): scalar, tiny. PL = 0:
+        // the column right of the windows instead, xi = XIN (x_in = xb0*S +
+        // XIN - 1), zero at and beyond the right image edge x = W (with W a
+        // multiple of 2*XB that element is the next row's first in memory)
+        constexpr int XI_COL = PL ? 0 : XIN;
         for (int c = tid; c < YIN * CIN_T; c += NW * WAVE_SIZE) {
             const int ci = c % CIN_T;
             const int ry = c / CIN_T;
-            const int y_in = yb0 * S - 1 + ry;
-            const int x_in = xb0 * S - 1;
+            const int y_in = yb0 * S - PL + ry;
+            const int x_in = xb0 * S - 1 + XI_COL;
             const int cin = cin0 + ci;
             uint16_t val = 0;
-            if (x_in >= 0 && cin < p.Cin) {
+            if (x_in >= 0 && (PL || x_in < p.W) && cin < p.Cin) {
                 if (y_in >= 0 && y_in < p.H)
                     val = xin[(int64_t)cin * p.x_sc + (int64_t)y_in * p.W + x_in];
                 else if (y_in == -1 && top)
@@ -302,8 +315,11 @@ __global__ __launch_bounds__(YB * XW * WAVE_SIZE) void conv3x3_kernel(Conv3x3Par
                 else if (y_in == p.H && bot)
                     val = bot[(int64_t)cin * p.b_sc + x_in];
             }
-            // xi = 0: plane 0, row 0 for both strides
-            *reinterpret_cast<uint16_t*>(&inb[((0 * YIN + ry) * XP + 0) * ROW_P + ci * 2]) = val;
+            // xi = 0: plane 0, row 0 for both strides; xi = XIN: plane 1, row XB
+            constexpr int CPLANE = (S == 1) ? 0 : (XI_COL & 1);
+            constexpr int CROW = (S == 1) ? XI_COL : (XI_COL >> 1);
+            *reinterpret_cast<uint16_t*>(
+                &inb[((CPLANE * YIN + ry) * XP + CROW) * ROW_P + ci * 2]) = val;
         }
     };
     auto compute_tile = [&](char* inb, char* wb) {
@@ -319,7 +335,7 @@ __global__ __launch_bounds__(YB * XW * WAVE_SIZE) void conv3x3_kernel(Conv3x3Par
                     short8 bfrag[PW];
 #pragma unroll
                     for (int px = 0; px < PW; ++px) {
-                        const int xi = ((wx * PW + px) * 32 + lo) * S + dx;
+                        const int xi = ((wx * PW + px) * 32 + lo) * S + dx + (1 - PL);
                         const int plane = (S == 1) ? 0 : (xi & 1);
                         const int row = (S == 1) ? xi : (xi >> 1);
                         const char* baddr = &inb[((plane * YIN + ry) * XP + row) * ROW_P +
@@ -435,8 +451,12 @@ static void launch_conv3x3_t(const Conv3x3Params& p, int stride, hipStream_t str
         const int npix = nxb * nyb * p.B;
         const int ncb = (p.CT + NCT - 1) / NCT;
         dim3 grid((unsigned)(8 * ncb * ((npix + 7) / 8)));
-        conv3x3_kernel<2, YB, XW, 16, NCT, PW, F16>
-            <<<grid, dim3(YB * XW * WAVE_SIZE), 0, stream>>>(p);
+        if (p.pad_lo == 0)
+            conv3x3_kernel<2, YB, XW, 16, NCT, PW, F16, 0>
+                <<<grid, dim3(YB * XW * WAVE_SIZE), 0, stream>>>(p);
+        else
+            conv3x3_kernel<2, YB, XW, 16, NCT, PW, F16>
+                <<<grid, dim3(YB * XW * WAVE_SIZE), 0, stream>>>(p);
     }
 }
 

@@ -61,6 +61,10 @@ struct Conv3x3Params {
     int B, Cin, Cout, H, W, Ho, Wo;
     int KS, CT;
     int debug;  // 1 = skip input staging, 2 = skip MFMA (phase-cost probes)
+    // 1: pad 1 on every side. 0 (stride 2 only): pad bottom/right alone, the
+    // AutoencoderKL downsample; Ho = (H-2)/2 + 1, Wo = (W-2)/2 + 1, top null,
+    // row H reads bot (or zero), column W is zero.
+    int pad_lo;
     int64_t x_sb, x_sc;
     int64_t t_sb, t_sc;
     int64_t b_sb, b_sc;

@@ -1,4 +1,4 @@
-"""Native VAE (AutoencoderKL) decoder.
+"""Native VAE (AutoencoderKL) decoder and encoder.
 
 The reference delegated VAE decode to diffusers; here it is owned. Every
 rank decodes the identical full latent (parity with the reference's
@@ -8,6 +8,10 @@ attention (single 512-dim head over up to 480x480 = 230k tokens at
 GPU; the CPU path uses a query-chunked softmax so no full score matrix is
 ever materialized. Convolutions ride the implicit-GEMM conv3x3 kernel
 (NativeConv2d).
+
+The encoder (img2img) is built from the same blocks: its three downsample
+convs are 3x3 stride-2 convs padded on the bottom and right only, which is
+the conv kernel's pad_lo=0 mode (NativeConv2d(asym_pad=True)).
 """
 
 from __future__ import annotations
@@ -31,6 +35,9 @@ class VAEDecoderConfig:
     layers_per_block: int = 2
     norm_num_groups: int = 32
     scaling_factor: float = 0.13025  # SDXL
+    # encoder side (VAEEncoder); the decoder reads neither
+    in_channels: int = 3
+    double_z: bool = True
 
 
 SDXL_VAE = VAEDecoderConfig()
@@ -258,3 +265,192 @@ class VAEDecoder(nn.Module):
         return self._decode_one(z)
 
     forward = decode
+
+
+class DownEncoderBlock2D(nn.Module):
+    def __init__(self, in_ch: int, out_ch: int, layers: int, add_downsample: bool, groups: int):
+        super().__init__()
+        self.resnets = nn.ModuleList(
+            [VAEResnetBlock(in_ch if i == 0 else out_ch, out_ch, groups) for i in range(layers)]
+        )
+        # AutoencoderKL downsample: F.pad(x, (0, 1, 0, 1)) then a padding-0
+        # stride-2 conv, i.e. padded on the bottom and right only
+        self.downsampler = (NativeConv2d(out_ch, out_ch, 3, stride=2, padding=0, asym_pad=True)
+                            if add_downsample else None)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        for r in self.resnets:
+            x = r(x)
+        if self.downsampler is not None:
+            x = self.downsampler(x)
+        return x
+
+
+class VAEEncoder(nn.Module):
+    """AutoencoderKL encoder: images in [-1, 1] -> posterior moments -> latents.
+
+    Built from the decoder's config values and blocks. ``encode`` returns
+    latents already multiplied by ``scaling_factor``, the inverse convention
+    of ``VAEDecoder.decode``.
+    """
+
+    LOGVAR_MIN, LOGVAR_MAX = -30.0, 20.0
+    SPATIAL = 8  # image pixels per latent pixel
+    # either latent side at or above this tiles the call automatically: the
+    # mid attention is O(L^2) in latent tokens, the wall the decoder hit
+    auto_tiling_min_latent = 256
+
+    def __init__(self, config: VAEDecoderConfig):
+        super().__init__()
+        self.config = config
+        ch = config.block_out_channels
+        groups = config.norm_num_groups
+        assert len(ch) == 4, "the encoder downsamples by 8: four down blocks"
+        self.conv_in = NativeConv2d(config.in_channels, ch[0], 3, padding=1)
+        blocks = []
+        prev = ch[0]
+        for i, out_ch in enumerate(ch):
+            blocks.append(
+                DownEncoderBlock2D(prev, out_ch, config.layers_per_block,
+                                   add_downsample=i < len(ch) - 1, groups=groups)
+            )
+            prev = out_ch
+        self.down_blocks = nn.ModuleList(blocks)
+        top = ch[-1]
+        self.mid_resnet_1 = VAEResnetBlock(top, top, groups)
+        self.mid_attn = VAEAttention(top, groups)
+        self.mid_resnet_2 = VAEResnetBlock(top, top, groups)
+        self.conv_norm_out = nn.GroupNorm(groups, top, eps=1e-6)
+        zc = config.latent_channels * (2 if config.double_z else 1)
+        self.conv_out = NativeConv2d(top, zc, 3, padding=1)
+        self.quant_conv = NativeConv2d(zc, zc, 1)
+
+    # -- tiled encode (diffusers AutoencoderKL.tiled_encode parity) ---------
+    # Same names and defaults as the decoder; sizes are in latent pixels, so a
+    # tile is tile_latent_size * 8 image pixels.
+    use_tiling: bool = False
+    tile_latent_size: int = 96
+    tile_overlap: int = 16
+
+    def enable_tiling(self, tile_latent_size: int = 96, tile_overlap: int = 16) -> None:
+        self.use_tiling = True
+        self.tile_latent_size = tile_latent_size
+        self.tile_overlap = tile_overlap
+
+    def disable_tiling(self) -> None:
+        self.use_tiling = False
+
+    @torch.no_grad()
+    def _encode_one(self, x: torch.Tensor) -> torch.Tensor:
+        """images -> moments [B, 2*latent_channels, H/8, W/8] (after quant_conv)."""
+        x = self.conv_in(x)
+        for block in self.down_blocks:
+            x = block(x)
+        x = self.mid_resnet_1(x)
+        x = self.mid_attn(x)
+        x = self.mid_resnet_2(x)
+        x = ops.group_norm_silu(x, self.conv_norm_out.num_groups, self.conv_norm_out.weight,
+                                self.conv_norm_out.bias, self.conv_norm_out.eps)
+        return self.quant_conv(self.conv_out(x))
+
+    @torch.no_grad()
+    def _encode_tiled(self, x: torch.Tensor) -> torch.Tensor:
+        sf = self.SPATIAL
+        ts, ov = self.tile_latent_size, self.tile_overlap
+        stride = ts - ov
+        ts_px, ov_px, st_px = ts * sf, ov * sf, stride * sf
+        b, _, h, w = x.shape
+        ys = list(range(0, max(h - ov_px, 1), st_px))
+        xs = list(range(0, max(w - ov_px, 1), st_px))
+        # full-size tiles encode as ONE batched pass, ragged edge tiles one
+        # by one (as the decoder does)
+        tiles = {}
+        full = [(y0, x0) for y0 in ys for x0 in xs
+                if y0 + ts_px <= h and x0 + ts_px <= w]
+        if len(full) > 1 and b == 1:
+            batch = torch.cat([x[:, :, y0 : y0 + ts_px, x0 : x0 + ts_px]
+                               for (y0, x0) in full])
+            enc = self._encode_one(batch)
+            for i, key in enumerate(full):
+                tiles[key] = enc[i : i + 1]
+        for y0 in ys:
+            for x0 in xs:
+                if (y0, x0) not in tiles:
+                    tiles[(y0, x0)] = self._encode_one(
+                        x[:, :, y0 : y0 + ts_px, x0 : x0 + ts_px])
+        rows = [[tiles[(y0, x0)] for x0 in xs] for y0 in ys]
+
+        # the MOMENTS are blended, linearly across the overlap, before sampling
+        def blend_v(a, bt, k):
+            k = min(k, a.shape[2], bt.shape[2])
+            w_ = torch.linspace(0, 1, k, device=a.device, dtype=a.dtype).view(1, 1, k, 1)
+            bt[:, :, :k] = a[:, :, a.shape[2] - k :] * (1 - w_) + bt[:, :, :k] * w_
+            return bt
+
+        def blend_h(a, bt, k):
+            k = min(k, a.shape[3], bt.shape[3])
+            w_ = torch.linspace(0, 1, k, device=a.device, dtype=a.dtype).view(1, 1, 1, k)
+            bt[:, :, :, :k] = a[:, :, :, a.shape[3] - k :] * (1 - w_) + bt[:, :, :, :k] * w_
+            return bt
+
+        out_rows = []
+        for i, row in enumerate(rows):
+            parts = []
+            for j, tile in enumerate(row):
+                if i > 0:
+                    tile = blend_v(rows[i - 1][j], tile, ov)
+                if j > 0:
+                    tile = blend_h(row[j - 1], tile, ov)
+                keep_w = stride if j < len(row) - 1 else tile.shape[3]
+                parts.append(tile[:, :, :stride, :keep_w] if i < len(rows) - 1
+                             else tile[:, :, :, :keep_w])
+            out_rows.append(torch.cat(parts, dim=3))
+        out = torch.cat(out_rows, dim=2)
+        return out[:, :, : h // sf, : w // sf]
+
+    @torch.no_grad()
+    def encode_moments(self, images: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+        """images [B, in_channels, H, W] in [-1, 1] -> (mean, logvar), each
+        [B, latent_channels, H/8, W/8]; logvar is clamped to [-30, 20].
+
+        A call whose latent would have a side >= ``auto_tiling_min_latent``
+        runs tiled with the default tile settings for that call only; the
+        tiling state it found is restored afterwards.
+        """
+        sf = self.SPATIAL
+        lh, lw = images.shape[2] // sf, images.shape[3] // sf
+        saved = (self.use_tiling, self.tile_latent_size, self.tile_overlap)
+        auto = not self.use_tiling and max(lh, lw) >= self.auto_tiling_min_latent
+        if auto:
+            self.enable_tiling()
+        try:
+            if self.use_tiling and (lh > self.tile_latent_size or lw > self.tile_latent_size):
+                moments = self._encode_tiled(images)
+            else:
+                moments = self._encode_one(images)
+        finally:
+            self.use_tiling, self.tile_latent_size, self.tile_overlap = saved
+        if not self.config.double_z:
+            return moments, torch.full_like(moments, self.LOGVAR_MIN)
+        mean, logvar = moments.chunk(2, dim=1)
+        return mean, logvar.clamp(self.LOGVAR_MIN, self.LOGVAR_MAX)
+
+    @torch.no_grad()
+    def encode(self, images: torch.Tensor, generator: torch.Generator | None = None,
+               sample: bool = True) -> torch.Tensor:
+        """images in [-1, 1] -> latents times ``scaling_factor``.
+
+        ``sample=False`` returns the posterior mode. The sampling noise is
+        drawn in fp32 from ``generator`` on the generator's device (the CPU
+        by default) and then moved to the model's, the rule the pipelines
+        follow for the initial latents: every rank draws identical noise.
+        """
+        mean, logvar = self.encode_moments(images)
+        if not sample:
+            return mean * self.config.scaling_factor
+        device = generator.device if generator is not None else torch.device("cpu")
+        noise = torch.randn(mean.shape, generator=generator, dtype=torch.float32, device=device)
+        z = mean.float() + torch.exp(0.5 * logvar.float()) * noise.to(mean.device)
+        return (z * self.config.scaling_factor).to(mean.dtype)
+
+    forward = encode

@@ -12,6 +12,7 @@ Deliberate layout deviations handled here:
 * GEGLU ``ff.net.0.proj`` / ``ff.net.2``   ->  ``ff.proj_in`` / ``ff.proj_out``
 * PatchConv2d wraps an inner nn.Conv2d (adds a ``.conv`` path segment)
 * VAE decoder: our flat names <-> diffusers ``decoder.*`` structure
+* VAE encoder: likewise ``encoder.*``, with ``quant_conv`` at the top level
 * CLIP: our flat names <-> HF ``text_model.*`` structure
 """
 
@@ -58,6 +59,19 @@ _VAE_RENAMES = [
     (re.compile(r"^conv_out\."), "decoder.conv_out."),
 ]
 
+_VAE_ENCODER_RENAMES = [
+    (re.compile(r"^conv_in\."), "encoder.conv_in."),
+    (re.compile(r"^down_blocks\.(\d+)\.downsampler\."),
+     r"encoder.down_blocks.\1.downsamplers.0.conv."),
+    (re.compile(r"^down_blocks\."), "encoder.down_blocks."),
+    (re.compile(r"^mid_resnet_1\."), "encoder.mid_block.resnets.0."),
+    (re.compile(r"^mid_attn\."), "encoder.mid_block.attentions.0."),
+    (re.compile(r"^mid_resnet_2\."), "encoder.mid_block.resnets.1."),
+    (re.compile(r"^conv_norm_out\."), "encoder.conv_norm_out."),
+    (re.compile(r"^conv_out\."), "encoder.conv_out."),
+    # quant_conv.* keeps its name (top level of the AutoencoderKL file)
+]
+
 _CLIP_RENAMES = [
     (re.compile(r"^token_embedding\."), "text_model.embeddings.token_embedding."),
     (re.compile(r"^position_embedding\."), "text_model.embeddings.position_embedding."),
@@ -83,10 +97,12 @@ def _renamed_key_map(model: nn.Module, renames) -> dict[str, str]:
 
 def key_map_for(model: nn.Module) -> dict[str, str]:
     from .clip import CLIPTextEncoder
-    from .vae import VAEDecoder
+    from .vae import VAEDecoder, VAEEncoder
 
     if isinstance(model, VAEDecoder):
         return _renamed_key_map(model, _VAE_RENAMES)
+    if isinstance(model, VAEEncoder):
+        return _renamed_key_map(model, _VAE_ENCODER_RENAMES)
     if isinstance(model, CLIPTextEncoder):
         return _renamed_key_map(model, _CLIP_RENAMES)
     return _unet_key_map(model)

@@ -5,6 +5,8 @@ top/bottom halo rows are read from separate tensors — e.g. the displaced-
 patch comm buffer — instead of a materialized cat (reference
 /root/reference/distrifuser/modules/pp/conv2d.py:72-88 concatenates).
 Weights are prepacked once into the kernel's per-lane MFMA A-fragment order.
+``pad_lo=0`` selects the kernel's stride-2 mode padded on the bottom and right
+only (the AutoencoderKL encoder downsample).
 """
 
 from __future__ import annotations
@@ -54,11 +56,12 @@ def _hip_conv_ok(x: torch.Tensor, stride: int) -> bool:
 
 
 def conv3x3_halo(x, weight, bias, stride=1, top=None, bot=None, packed=None, residual=None,
-                 bias2=None):
+                 bias2=None, pad_lo=1):
     """Dispatching halo conv. ``packed`` (from :func:`pack_conv3x3_weight`)
     enables the HIP path; eager falls back to the cat-based oracle.
     ``residual`` ([B,Cout,Ho,Wo]) and ``bias2`` ([B,Cout], the time-embedding
-    add) are applied in the kernel epilogue."""
+    add) are applied in the kernel epilogue. ``pad_lo=0`` (stride 2, no
+    ``top``) pads the bottom and right only: the AutoencoderKL downsample."""
     import os
     # In-epilogue residual measured ~0.7% SLOWER end-to-end than a separate
     # add kernel (the epilogue's cout-strided 2 B residual reads are poorly
@@ -66,15 +69,17 @@ def conv3x3_halo(x, weight, bias, stride=1, top=None, bot=None, packed=None, res
     # DFA_CONV_RESID=1. bias2 is one scalar per output ROW (like the conv
     # bias) and is free, so it stays on by default.
     if residual is not None and os.environ.get("DFA_CONV_RESID", "0") != "1":
-        out = conv3x3_halo(x, weight, bias, stride, top, bot, packed=packed, bias2=bias2)
+        out = conv3x3_halo(x, weight, bias, stride, top, bot, packed=packed, bias2=bias2,
+                           pad_lo=pad_lo)
         return out + residual
     if _use_hip(x) and packed is not None and _hip_conv_ok(x, stride):
         cout = weight.shape[0]
         t = top.reshape(top.shape[0], top.shape[1], -1) if top is not None else None
         b = bot.reshape(bot.shape[0], bot.shape[1], -1) if bot is not None else None
         if (t is None or t.stride(-1) == 1) and (b is None or b.stride(-1) == 1):
-            return hip_ext().conv3x3(x, packed, bias, cout, stride, t, b, residual, bias2)
-    out = eager.conv3x3_halo(x, weight, bias, stride, top, bot)
+            return hip_ext().conv3x3(x, packed, bias, cout, stride, t, b, residual, bias2,
+                                     pad_lo)
+    out = eager.conv3x3_halo(x, weight, bias, stride, top, bot, pad_lo)
     if bias2 is not None:
         out = out + bias2.to(out.dtype)[:, :, None, None]
     return out if residual is None else out + residual
@@ -86,10 +91,19 @@ class NativeConv2d(nn.Conv2d):
     State-dict compatible with nn.Conv2d (same parameters); the packed
     fragment-order weight copy is built lazily on first GPU forward and
     cached until the weight storage changes.
+
+    ``asym_pad=True`` (3x3, stride 2, padding 0) is the AutoencoderKL
+    downsample: the input is padded on the bottom and right only. On GPU that
+    is the kernel's ``pad_lo=0`` mode; elsewhere ``F.pad(x, (0, 1, 0, 1))``
+    and the padding-0 conv. The flag adds no parameter or buffer.
     """
 
-    def __init__(self, *args, **kwargs):
+    def __init__(self, *args, asym_pad: bool = False, **kwargs):
         super().__init__(*args, **kwargs)
+        if asym_pad and not (self.kernel_size == (3, 3) and self.stride == (2, 2)
+                             and self.padding == (0, 0)):
+            raise ValueError("asym_pad needs a 3x3 conv with stride 2 and padding 0")
+        self.asym_pad = asym_pad
         self._wp = None
         self._wp_key = None
 
@@ -97,7 +111,7 @@ class NativeConv2d(nn.Conv2d):
         return (
             x.is_cuda
             and self.kernel_size == (3, 3)
-            and self.padding == (1, 1)
+            and self.padding == ((0, 0) if self.asym_pad else (1, 1))
             and self.stride[0] == self.stride[1]
             and self.stride[0] in (1, 2)
             and self.dilation == (1, 1)
@@ -127,6 +141,7 @@ class NativeConv2d(nn.Conv2d):
             return conv3x3_halo(
                 x, self.weight, self.bias, self.stride[0], top, bot,
                 packed=self.packed_weight(), residual=residual, bias2=bias2,
+                pad_lo=0 if self.asym_pad else 1,
             )
         if (
             x.is_cuda
@@ -145,7 +160,9 @@ class NativeConv2d(nn.Conv2d):
             if self.bias is not None:
                 out = out + self.bias.view(1, -1, 1)
             return out.view(b, self.out_channels, h, w)
-        if top is None and bot is None:
+        if self.asym_pad:
+            out = eager.conv3x3_halo(x, self.weight, self.bias, 2, top, bot, pad_lo=0)
+        elif top is None and bot is None:
             out = super().forward(x)
         else:
             out = eager.conv3x3_halo(x, self.weight, self.bias, self.stride[0], top, bot)

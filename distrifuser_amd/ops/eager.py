@@ -159,6 +159,7 @@ def conv3x3_halo(
     stride: int = 1,
     top: torch.Tensor | None = None,
     bot: torch.Tensor | None = None,
+    pad_lo: int = 1,
 ) -> torch.Tensor:
     """3x3 pad-1 conv whose top/bottom halo rows come from separate tensors.
 
@@ -167,8 +168,22 @@ def conv3x3_halo(
     materializes cat([top, x, bot]) per conv
     (/root/reference/distrifuser/modules/pp/conv2d.py:72-88); the kernel —
     and this oracle — treat the halos as extra input rows in place.
+
+    pad_lo=0 (stride 2 only, no top) is the AutoencoderKL downsample: the
+    input is padded on the bottom and right alone, F.pad(x, (0, 1, 0, 1)) then
+    a padding=0 conv, so output (y, x) reads rows 2y..2y+2 and columns
+    2x..2x+2. Row H is bot when given, else zero; column W is zero.
     """
     b, c, h, w = x.shape
+    if pad_lo == 0:
+        if stride != 2 or top is not None or h < 2 or w < 2:
+            raise ValueError("conv3x3_halo: pad_lo=0 needs stride 2, no top halo and H, W >= 2")
+        full = x if bot is None else torch.cat([x, bot.reshape(b, c, 1, w)], dim=2)
+        full = F.pad(full, [0, 1, 0, 1 if bot is None else 0])
+        out = F.conv2d(full, weight, bias, stride=2)
+        return out[:, :, : (h - 2) // 2 + 1, :]
+    if pad_lo != 1:
+        raise ValueError(f"conv3x3_halo: pad_lo must be 0 or 1, got {pad_lo}")
     parts = []
     pad_top = 1 if top is None else 0
     pad_bot = 1 if bot is None else 0

@@ -23,9 +23,10 @@ from .models.clip import CLIP_VIT_L, OPEN_CLIP_BIG_G, TINY_CLIP, CLIPTextEncoder
 from .models.distri_unet import DistriUNet
 from .models.tokenizer import CLIPBPETokenizer, SimpleTokenizer, load_clip_tokenizer
 from .models.unet import SD15_UNET, SDXL_UNET, TINY_UNET, UNetConfig
-from .models.vae import SD_VAE, SDXL_VAE, TINY_VAE, VAEDecoder
+from .models.vae import SD_VAE, SDXL_VAE, TINY_VAE, VAEDecoder, VAEEncoder
 from .models import weights as weight_io
 from .schedulers import get_scheduler
+from .schedulers.common import img2img_start
 from .utils.comm import PatchParallelismCommManager
 from .utils.config import DistriConfig
 
@@ -72,6 +73,11 @@ def _maybe_tqdm(iterable, enabled: bool):
 
 class _DistriPipelineBase:
     is_sdxl = False
+    # img2img: the VAE encoder is built on first use (the vae_encoder
+    # accessor), so a text-to-image pipeline allocates nothing for it
+    _vae_encoder: VAEEncoder | None = None
+    _pretrained_path: str | None = None  # from_pretrained's checkpoint directory
+    _ENCODER_SEED = 0x1E2C0DE  # random-init stream of the encoder, its own
 
     def __init__(
         self,
@@ -105,6 +111,8 @@ class _DistriPipelineBase:
         from .models.weights import export_diffusers_state_dict
 
         components = {"unet": self.unet.unet, "vae": self.vae}
+        # the encoder's keys share the vae file, once an encoder has been built
+        extra = {"vae": self._vae_encoder} if self._vae_encoder is not None else {}
         if hasattr(self, "text_encoder"):
             components["text_encoder"] = self.text_encoder
         if hasattr(self, "text_encoder_2"):
@@ -112,6 +120,9 @@ class _DistriPipelineBase:
         for name, model in components.items():
             os.makedirs(os.path.join(out_dir, name), exist_ok=True)
             sd = {k: v.contiguous().cpu() for k, v in export_diffusers_state_dict(model).items()}
+            if name in extra:
+                sd.update({k: v.contiguous().cpu()
+                           for k, v in export_diffusers_state_dict(extra[name]).items()})
             # diffusers repo layout: unet/vae use diffusion_pytorch_model.*,
             # text encoders use model.* (ADVICE r1 — keeps the export loadable
             # by upstream diffusers, not just our own from_pretrained).
@@ -152,12 +163,100 @@ class _DistriPipelineBase:
         latents = latents.to(device=cfg.device, dtype=self._unet_dtype())
         return latents * self.scheduler.init_noise_sigma
 
-    def _denoise(self, latents, prompt_embeds, added_cond_kwargs, num_inference_steps, guidance_scale):
+    # -- img2img ---------------------------------------------------------------
+
+    @property
+    def vae_encoder(self) -> VAEEncoder:
+        """The VAE encoder, built on first access.
+
+        It is built inside ``torch.random.fork_rng`` from a fixed seed of its
+        own, so building it never advances the global CPU or GPU generators
+        (``from_pretrained``'s seeded construction order is untouched), and it
+        loads the checkpoint's ``encoder.*`` / ``quant_conv.*`` weights when
+        the pipeline came from a checkpoint directory."""
+        if self._vae_encoder is None:
+            with torch.random.fork_rng(devices=[]):
+                # the CPU generator only: modules are initialised on the CPU
+                torch.default_generator.manual_seed(self._ENCODER_SEED)
+                enc = VAEEncoder(self.vae.config)
+            if self._pretrained_path is not None:
+                path = weight_io.find_component_weights(self._pretrained_path, "vae")
+                if path is not None:
+                    weight_io.load_into(enc, weight_io.load_safetensors(path))
+            ref = next(self.vae.parameters())
+            self._vae_encoder = enc.to(device=ref.device, dtype=ref.dtype).eval()
+        return self._vae_encoder
+
+    def _prepare_image(self, image) -> torch.Tensor:
+        """A float tensor [3,H,W] / [1,3,H,W] in [0, 1], a uint8 HWC numpy
+        array or a PIL image -> [1,3,H,W] in [-1, 1] on the model device. H, W
+        must be DistriConfig's: nothing is resized."""
+        cfg = self.distri_config
+        if not torch.is_tensor(image):
+            import numpy as np
+
+            if not isinstance(image, np.ndarray):
+                try:
+                    from PIL import Image
+                except ImportError:
+                    Image = None
+                if Image is None or not isinstance(image, Image.Image):
+                    raise TypeError(f"image: unsupported type {type(image).__name__}")
+                image = np.array(image.convert("RGB"))
+            if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+                raise ValueError("image: a numpy image must be uint8 [H, W, 3], got "
+                                 f"{image.dtype} {image.shape}")
+            image = torch.from_numpy(np.ascontiguousarray(image)).permute(2, 0, 1).float() / 255.0
+        elif not image.is_floating_point():
+            raise ValueError("image: a tensor image must be floating point in [0, 1]")
+        if image.dim() == 3:
+            image = image[None]
+        if image.dim() != 4 or image.shape[0] != 1 or image.shape[1] != 3:
+            raise ValueError(f"image: expected [3,H,W] or [1,3,H,W], got {tuple(image.shape)}")
+        if tuple(image.shape[2:]) != (cfg.height, cfg.width):
+            raise ValueError(
+                f"image is {image.shape[2]}x{image.shape[3]} but the pipeline is built for "
+                f"{cfg.height}x{cfg.width} (DistriConfig); resize it first")
+        image = image.float() * 2.0 - 1.0
+        return image.to(device=cfg.device, dtype=next(self.vae.parameters()).dtype)
+
+    def _img2img_latents(self, image, strength: float, num_inference_steps: int, generator):
+        """Encode ``image``, sample the posterior, and noise it to the first
+        executed timestep. Returns (latents, t_start). Every rank encodes the
+        full image (replicated work, as decode is) and, drawing from equal
+        generators, holds identical latents. The posterior sample is drawn
+        first and the noise after it, from the same generator."""
+        t_start = img2img_start(num_inference_steps, strength)
+        pixels = self._prepare_image(image)
+        if generator is None:
+            generator = torch.Generator().manual_seed(0)  # same on every rank
+        from .utils.tracing import trace_range
+
+        with trace_range("vae_encode"):
+            init = self.vae_encoder.encode(pixels, generator=generator)
+        device = generator.device if hasattr(generator, "device") else torch.device("cpu")
+        noise = torch.randn(init.shape, generator=generator, dtype=torch.float32, device=device)
+        self.scheduler.set_timesteps(num_inference_steps, device=None)
+        # strength = 1 still noises the image at the first timestep; and no
+        # init_noise_sigma here: add_noise already lands on sigma_t
+        latents = self.scheduler.add_noise(init.float(), noise.to(init.device),
+                                           self.scheduler.timesteps[t_start])
+        return latents.to(self._unet_dtype()), t_start
+
+    def _denoise(self, latents, prompt_embeds, added_cond_kwargs, num_inference_steps,
+                 guidance_scale, t_start: int = 0):
+        """``t_start > 0`` (img2img) runs the last n - t_start steps only. The
+        U-Net counter is 0 at the first step that actually runs, so the
+        ``warmup_steps`` synchronous steps of displaced patch parallelism are
+        counted from there, and the captured graphs and ``_graph_counters``
+        are the text-to-image ones."""
         cfg = self.distri_config
         do_cfg = cfg.do_classifier_free_guidance
         from .utils.tracing import trace_range
 
         self.scheduler.set_timesteps(num_inference_steps, device=None)
+        if t_start:
+            self.scheduler.set_begin_index(t_start)
         self.unet.set_counter(0)
         for i, t in enumerate(_maybe_tqdm(self.scheduler.timesteps, self._progress)):
             with trace_range(f"denoise_step_{i}"):
@@ -335,9 +434,11 @@ class DistriSDXLPipeline(_DistriPipelineBase):
         vae = vae.to(device=device, dtype=torch_dtype).eval()
         te1 = te1.to(device=device, dtype=torch_dtype).eval()
         te2 = te2.to(device=device, dtype=torch_dtype).eval()
-        return DistriSDXLPipeline(distri_config, unet, vae, te1, te2,
-                                  get_scheduler(scheduler), tokenizer,
-                                  tokenizer_2=tokenizer_2)
+        pipeline = DistriSDXLPipeline(distri_config, unet, vae, te1, te2,
+                                      get_scheduler(scheduler), tokenizer,
+                                      tokenizer_2=tokenizer_2)
+        pipeline._pretrained_path = pretrained  # for the lazily built VAE encoder
+        return pipeline
 
     @torch.no_grad()
     def encode_prompt(self, prompt, negative_prompt=None, do_classifier_free_guidance=True):
@@ -389,8 +490,17 @@ class DistriSDXLPipeline(_DistriPipelineBase):
         guidance_scale: float = 5.0,
         generator: torch.Generator | None = None,
         output_type: str = "pil",
+        image=None,
+        strength: float = 0.3,
         **kwargs,
     ):
+        """Text-to-image, or with ``image=`` img2img (SDEdit): the image (a
+        float tensor [3,H,W] / [1,3,H,W] in [0, 1], a uint8 HWC numpy array
+        or a PIL image, at DistriConfig's height x width) is encoded, noised
+        to ``strength`` and denoised over the last ``int(steps * strength)``
+        steps. The displaced-patch warmup counts from the first step that
+        runs (see ``_denoise``). The added time ids are the text-to-image
+        ones; there is no refiner aesthetic score."""
         assert "height" not in kwargs and "width" not in kwargs, (
             "height/width are fixed by DistriConfig (the comm buffers and "
             "graphs are sized for them)"
@@ -405,8 +515,14 @@ class DistriSDXLPipeline(_DistriPipelineBase):
         embeds = embeds.to(self._unet_dtype())
         pooled = pooled.to(self._unet_dtype())
         added = self._added_cond(embeds.shape[0], pooled)
-        latents = self._prepare_latents(1, generator)
-        latents = self._denoise(latents, embeds, added, num_inference_steps, guidance_scale)
+        t_start = 0
+        if image is None:
+            latents = self._prepare_latents(1, generator)
+        else:
+            latents, t_start = self._img2img_latents(image, strength, num_inference_steps,
+                                                     generator)
+        latents = self._denoise(latents, embeds, added, num_inference_steps, guidance_scale,
+                                t_start)
         return self._decode(latents, output_type)
 
 
@@ -463,7 +579,10 @@ class DistriSDPipeline(_DistriPipelineBase):
         unet = unet.to(device=device, dtype=torch_dtype).eval()
         vae = vae.to(device=device, dtype=torch_dtype).eval()
         te = te.to(device=device, dtype=torch_dtype).eval()
-        return DistriSDPipeline(distri_config, unet, vae, te, get_scheduler(scheduler), tokenizer)
+        pipeline = DistriSDPipeline(distri_config, unet, vae, te, get_scheduler(scheduler),
+                                    tokenizer)
+        pipeline._pretrained_path = pretrained  # for the lazily built VAE encoder
+        return pipeline
 
     @torch.no_grad()
     def encode_prompt(self, prompt, negative_prompt=None, do_classifier_free_guidance=True):
@@ -497,14 +616,24 @@ class DistriSDPipeline(_DistriPipelineBase):
         guidance_scale: float = 7.5,
         generator: torch.Generator | None = None,
         output_type: str = "pil",
+        image=None,
+        strength: float = 0.3,
         **kwargs,
     ):
+        """Text-to-image, or img2img with ``image=`` / ``strength=`` (see
+        ``DistriSDXLPipeline.__call__``)."""
         assert "height" not in kwargs and "width" not in kwargs
         cfg = self.distri_config
         if not cfg.do_classifier_free_guidance:
             guidance_scale = 1
         do_cfg = cfg.do_classifier_free_guidance
         embeds = self.encode_prompt(prompt, negative_prompt, do_cfg).to(self._unet_dtype())
-        latents = self._prepare_latents(1, generator)
-        latents = self._denoise(latents, embeds, None, num_inference_steps, guidance_scale)
+        t_start = 0
+        if image is None:
+            latents = self._prepare_latents(1, generator)
+        else:
+            latents, t_start = self._img2img_latents(image, strength, num_inference_steps,
+                                                     generator)
+        latents = self._denoise(latents, embeds, None, num_inference_steps, guidance_scale,
+                                t_start)
         return self._decode(latents, output_type)

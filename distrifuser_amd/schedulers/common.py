@@ -46,3 +46,38 @@ class SchedulerBase:
 
     def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor) -> torch.Tensor:
         raise NotImplementedError
+
+    # -- img2img: forward noising and a part-way start -----------------------
+
+    def add_noise(self, sample: torch.Tensor, noise: torch.Tensor, timestep) -> torch.Tensor:
+        """q(x_t | x_0): sqrt(acp_t) * sample + sqrt(1 - acp_t) * noise, in fp32,
+        returned in sample's dtype."""
+        acp = self.alphas_cumprod[int(timestep)]
+        out = acp.sqrt() * sample.float() + (1 - acp).sqrt() * noise.float().to(sample.device)
+        return out.to(sample.dtype)
+
+    def set_begin_index(self, t_start: int) -> None:
+        """Start the schedule at index ``t_start`` of the list that
+        ``set_timesteps(n)`` made: ``timesteps`` becomes its last n - t_start
+        entries, and every step computes what the full schedule computes at
+        that index (the multistep solver takes its first executed step as
+        first order: it has no history). Call it once, right after
+        ``set_timesteps``."""
+        n = len(self.timesteps)
+        if not 0 <= t_start < n:
+            raise ValueError(f"t_start must be in [0, {n}), got {t_start}")
+        self.timesteps = self.timesteps[t_start:]
+
+
+def img2img_start(num_inference_steps: int, strength: float) -> int:
+    """Index of the first executed step for an img2img ``strength`` (the
+    diffusers rule): init = min(int(n * strength), n) steps run, so
+    t_start = max(n - init, 0). strength must be in (0, 1] and leave at least
+    one step."""
+    if not 0 < strength <= 1:
+        raise ValueError(f"strength must be in (0, 1], got {strength}")
+    init = min(int(num_inference_steps * strength), num_inference_steps)
+    if init < 1:
+        raise ValueError(
+            f"strength {strength} leaves no step to run out of {num_inference_steps}")
+    return max(num_inference_steps - init, 0)

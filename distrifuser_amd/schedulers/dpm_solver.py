@@ -28,6 +28,13 @@ class DPMSolverMultistepScheduler(SchedulerBase):
         self._t_prev = None
         self._step_index = 0
 
+    def set_begin_index(self, t_start: int) -> None:
+        super().set_begin_index(t_start)
+        # no history: the first executed step is first order, the rest 2M
+        self._x0_prev = None
+        self._t_prev = None
+        self._step_index = 0
+
     def _prev_timestep(self, t: int) -> int:
         idx = int((self.timesteps == t).nonzero()[0])
         return int(self.timesteps[idx + 1]) if idx + 1 < len(self.timesteps) else 0

@@ -27,6 +27,18 @@ class EulerDiscreteScheduler(SchedulerBase):
         self.init_noise_sigma = float((self.sigmas.max() ** 2 + 1) ** 0.5)
         self._step_index = 0
 
+    def set_begin_index(self, t_start: int) -> None:
+        super().set_begin_index(t_start)
+        self.sigmas = self.sigmas[t_start:]  # sigmas[i] pairs with timesteps[i]
+        self._step_index = 0
+
+    def add_noise(self, sample: torch.Tensor, noise: torch.Tensor, timestep) -> torch.Tensor:
+        """sample + sigma_t * noise (init_noise_sigma is for pure noise only)."""
+        idx = int((self.timesteps == float(timestep)).nonzero()[0])
+        sigma = self.sigmas[idx]
+        out = sample.float() + sigma * noise.float().to(sample.device)
+        return out.to(sample.dtype)
+
     def scale_model_input(self, sample: torch.Tensor, timestep=None) -> torch.Tensor:
         sigma = self.sigmas[self._step_index]
         return sample / float((sigma**2 + 1) ** 0.5)

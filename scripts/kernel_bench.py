@@ -1,7 +1,8 @@
 """Quick on-box kernel A/B: our gfx950 kernels vs the PyTorch-ROCm baselines.
 
 Run on an MI355X: python scripts/kernel_bench.py > gpurun_out/kernel_bench.json
-(--splitkv-only: just the split-KV attention sweep; --dtype {bf16,fp16}: the
+(--splitkv-only: just the split-KV attention sweep; --vae-downsample-only:
+just the VAE-encoder downsample convs; --dtype {bf16,fp16}: the
 element type of the attention, conv, LayerNorm and VAE-attention rows, default
 bf16 — fp16 rows carry "dtype": "fp16")
 """
@@ -76,6 +77,40 @@ def splitkv_sweep(results, reps=5, iters=100):
         print(json.dumps(row), flush=True)
 
 
+def vae_downsample_rows(results, dt, tag, batches=(1, 25), reps=3):
+    """The three SDXL-VAE encoder downsample convs (3x3, stride 2, padded on
+    the bottom and right only) for 768^2 tiles: the kernel's pad_lo=0 mode
+    against F.pad + F.conv2d, interleaved `reps` times. Batch 25 is the
+    full-tile batch of a tiled 3840^2 encode. Reports the median and the
+    min..max spread of the repeats."""
+    from distrifuser_amd import ops
+
+    dev = "cuda:0"
+    for b in batches:
+        for c, hw in [(128, 768), (256, 384), (512, 192)]:
+            x = torch.randn(b, c, hw, hw, device=dev, dtype=dt) * 0.5
+            wt = torch.randn(c, c, 3, 3, device=dev, dtype=dt) * (c * 9) ** -0.5
+            bias = torch.randn(c, device=dev, dtype=dt)
+            packed = ops.pack_conv3x3_weight(wt, dt)
+            ours = lambda: ops.conv3x3_halo(x, wt, bias, 2, packed=packed, pad_lo=0)
+            ref = lambda: F.conv2d(F.pad(x, (0, 1, 0, 1)), wt, bias, stride=2)
+            err = (ours().float() - ref().float()).abs().max().item()
+            ms = {"ours": [], "miopen": []}
+            for _ in range(reps):
+                ms["ours"].append(timeit(ours))
+                ms["miopen"].append(timeit(ref))
+            flops = 2.0 * b * c * (hw // 2) ** 2 * c * 9
+            row = {**tag, "op": "conv3x3_pad_lo0", "batch": b, "c": c, "hw": hw, "reps": reps,
+                   "max_abs_diff": err}
+            for name, t in ms.items():
+                t = sorted(t)
+                row[f"ms_{name}"] = t[len(t) // 2]
+                row[f"spread_{name}"] = [t[0], t[-1]]
+                row[f"tflops_{name}"] = flops / t[len(t) // 2] / 1e9
+            results.append(row)
+            print(json.dumps(row), flush=True)
+
+
 def main():
     assert torch.cuda.is_available()
     from distrifuser_amd import ops
@@ -92,6 +127,11 @@ def main():
         splitkv_sweep(results)
         with open("kernel_bench_splitkv.json", "w") as f:
             json.dump(results, f, indent=1)
+        return 0
+
+    if "--vae-downsample-only" in sys.argv[1:]:
+        torch.backends.cudnn.benchmark = True
+        vae_downsample_rows(results, dt, tag)
         return 0
 
     # ---- flash attention at SDXL shapes (B=1 CFG-split branch) ----
@@ -169,6 +209,9 @@ def main():
             "tflops_miopen": flops / ms_ref / 1e9,
         })
         print(json.dumps(results[-1]), flush=True)
+
+    # ---- the VAE encoder's downsample convs (pad_lo=0) ----
+    vae_downsample_rows(results, dt, tag)
 
     # ---- fused GN+SiLU at SDXL shapes ----
     for c, hw in [(320, 480), (640, 240), (1280, 120), (320, 128), (640, 64)]:
