@@ -67,8 +67,8 @@ namespace {
 constexpr int QW = 32;     // q rows per wave
 constexpr int KVB = 128;   // kv tokens per LDS tile
 // split staging (issue-early / write-late) measured +1 % at L=57.6k and
-// +5-7 % on the chunked shapes against loading after the barrier
-constexpr bool SPLIT_STAGE = true;
+// +5-7 % on the chunked shapes against loading after the barrier; the kernel
+// has no other mode.
 // waves per block is a template parameter: bigger Q blocks amortize the KV
 // stream (each KV tile is re-read Lq/QBLK times), smaller blocks keep small
 // Lq shapes filled. Measured: 4w->8w at L=57.6k was +53% (439->673 TF).
@@ -77,8 +77,6 @@ constexpr bool SPLIT_STAGE = true;
 // 160). The real head_dim rides in FlashAttnParams.Dh; padding lanes carry
 // zeros (exact for QK^T scores and O columns < Dh).
 
-typedef float float4v_ __attribute__((ext_vector_type(4)));
-typedef float float16v __attribute__((ext_vector_type(16)));
 typedef short short4v __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) short4v lds_short4v;
 
@@ -146,7 +144,7 @@ __device__ __forceinline__ float half_sum(float v) {
 // F16: q/k/v/o are IEEE fp16 instead of bf16 — the two MFMAs, the P pack and
 // the output conversion change type; scores, max, sum, LSE and o_part stay
 // fp32 either way.
-template <int NW, int DPAD, bool DFULL, bool SPLIT, bool LSE, bool F16 = false>
+template <int NW, int DPAD, bool DFULL, bool LSE, bool F16>
 __global__ __launch_bounds__(NW * WAVE_SIZE)
 __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
     std::conditional_t<LSE, FlashAttnLseParams, FlashAttnParams> p, bool off32) {
@@ -374,6 +372,8 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const int t = st * 32 + lo;
+            // lds_frag_b64x2 spelled out: through the helper the DPAD-64 plain
+            // kernels schedule their staging writes differently
             const char* ksrc = &k_lds[t * K_ROW + (ks * 16 + hi * 8) * 2];
             const uint2 k0 = *reinterpret_cast<const uint2*>(ksrc);
             const uint2 k1 = *reinterpret_cast<const uint2*>(ksrc + 8);
@@ -393,15 +393,14 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
             float16v s_nxt;
             if (st + 1 < NST) s_nxt = qk_tile(st + 1);
             const float16v s = s_cur;
-            // lane holds S^T rows crow(r) = (r&3)+8*(r>>2)+4*hi for q col lo
+            // lane holds S^T rows mfma32_row(r, hi) for q col lo
             float tm = -1e30f;
             float pv[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 float v = s[r];
                 if (MASK) {
-                    const int crow = (r & 3) + 8 * (r >> 2) + 4 * hi;
-                    if (t0 + st * 32 + crow >= Lkv) v = -1e30f;
+                    if (t0 + st * 32 + mfma32_row(r, hi) >= Lkv) v = -1e30f;
                 }
                 pv[r] = v;
                 tm = fmaxf(tm, v);
@@ -487,14 +486,14 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
     for (int tile = tile0; tile < n_full; ++tile) {
         const int t0 = tile * KVB;
         const bool next_full = tile + 1 < n_full;
+        // split staging: the next tile's loads are in flight across the compute
         auto load_next = [&]() {
             if (next_full || rem) stage_load(t0 + KVB, next_full);
         };
-        if (SPLIT) load_next();
+        load_next();
         compute.template operator()<KVB / 32, false>(t0);
         if (next_full || rem) {
             lds_barrier();  // every wave is done reading this tile
-            if (!SPLIT) load_next();
             stage_write();
             lds_barrier();
         }
@@ -544,15 +543,10 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
         uint32_t ow[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            if constexpr (F16) {
+            if constexpr (F16)
                 ow[i] = cvt_pk_f16(ot[dt][2 * i] * inv, ot[dt][2 * i + 1] * inv);
-            } else {
-                const uint32_t e0 =
-                    __builtin_bit_cast(uint16_t, __float2bfloat16(ot[dt][2 * i] * inv));
-                const uint32_t e1 =
-                    __builtin_bit_cast(uint16_t, __float2bfloat16(ot[dt][2 * i + 1] * inv));
-                ow[i] = e0 | (e1 << 16);
-            }
+            else
+                ow[i] = pack2_b16<false>(ot[dt][2 * i] * inv, ot[dt][2 * i + 1] * inv);
         }
 #pragma unroll
         for (int g = 0; g < 4; g += 2) {
@@ -566,10 +560,6 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
         }
     }
 }
-
-}  // namespace
-
-namespace {
 
 // ---- merge of split-KV partials --------------------------------------------
 // One thread per (row, 8 d): S x two 16 B fp32 loads, one 16 B bf16/fp16 store (or
@@ -615,11 +605,7 @@ __global__ __launch_bounds__(256) void merge_attn_kernel(MergeAttnParams p) {
     if (OUT != DFA_F32) {
         uint32_t w[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint32_t e0 = f32_to_b16<OUT == DFA_F16>(acc[2 * j]);
-            const uint32_t e1 = f32_to_b16<OUT == DFA_F16>(acc[2 * j + 1]);
-            w[j] = e0 | (e1 << 16);
-        }
+        for (int j = 0; j < 4; ++j) w[j] = pack2_b16<OUT == DFA_F16>(acc[2 * j], acc[2 * j + 1]);
         *reinterpret_cast<uint4*>(static_cast<uint16_t*>(p.out) + row * p.Dh + dc * 8) =
             uint4{w[0], w[1], w[2], w[3]};
     } else {
@@ -656,84 +642,54 @@ bool fits_off32(const FlashAttnParams& p) {
     return sl >= 0 && sl * 2 * KVB + DPAD * 2 <= (int64_t)INT32_MAX;
 }
 
-template <int DPAD, bool F16>
-void launch_dpad_lse(const FlashAttnLseParams& p, int splits, hipStream_t stream) {
+// grid.z = splits; the plain (LSE = false) kernel takes the base slice of the
+// params and one split
+template <int DPAD, bool LSE, bool F16>
+void launch_dpad(const FlashAttnLseParams& p, int splits, hipStream_t stream) {
     constexpr int NW = 8;
     const int qblk = QW * NW;
-    dim3 grid((unsigned)((p.Lq + qblk - 1) / qblk), (unsigned)(p.B * p.H), (unsigned)splits);
-    dim3 block(NW * WAVE_SIZE);
+    const dim3 grid((unsigned)((p.Lq + qblk - 1) / qblk), (unsigned)(p.B * p.H),
+                    (unsigned)splits);
+    const dim3 block(NW * WAVE_SIZE);
     const bool off32 = fits_off32<DPAD>(p);
+    const std::conditional_t<LSE, FlashAttnLseParams, FlashAttnParams>& kp = p;
     if (p.Dh == DPAD)
-        flash_attn_kernel<NW, DPAD, true, SPLIT_STAGE, true, F16>
-            <<<grid, block, 0, stream>>>(p, off32);
+        flash_attn_kernel<NW, DPAD, true, LSE, F16><<<grid, block, 0, stream>>>(kp, off32);
     else
-        flash_attn_kernel<NW, DPAD, false, SPLIT_STAGE, true, F16>
-            <<<grid, block, 0, stream>>>(p, off32);
+        flash_attn_kernel<NW, DPAD, false, LSE, F16><<<grid, block, 0, stream>>>(kp, off32);
 }
 
-}  // namespace
-
-template <int DPAD, bool F16>
-static void launch_dpad(const FlashAttnParams& p, hipStream_t stream) {
-    constexpr int NW = 8;
-    const int qblk = QW * NW;
-    dim3 grid((unsigned)((p.Lq + qblk - 1) / qblk), (unsigned)(p.B * p.H));
-    dim3 block(NW * WAVE_SIZE);
-    const bool off32 = fits_off32<DPAD>(p);
-    if (p.Dh == DPAD)
-        flash_attn_kernel<NW, DPAD, true, SPLIT_STAGE, false, F16>
-            <<<grid, block, 0, stream>>>(p, off32);
-    else
-        flash_attn_kernel<NW, DPAD, false, SPLIT_STAGE, false, F16>
-            <<<grid, block, 0, stream>>>(p, off32);
-}
-
-template <bool F16>
-static void launch_plain(const FlashAttnParams& p, hipStream_t stream) {
+template <bool LSE, bool F16>
+void launch_ladder(const FlashAttnLseParams& p, int splits, hipStream_t stream) {
     // 8-wave (256-row) blocks measured best across the SD-family shapes;
     // every Lkv takes 128-token tiles plus a peeled tail. DPAD covers the
     // SD-family head dims.
     if (p.Dh <= 64)
-        launch_dpad<64, F16>(p, stream);
+        launch_dpad<64, LSE, F16>(p, splits, stream);
     else if (p.Dh <= 96)
-        launch_dpad<96, F16>(p, stream);
+        launch_dpad<96, LSE, F16>(p, splits, stream);
     else if (p.Dh <= 128)
-        launch_dpad<128, F16>(p, stream);
+        launch_dpad<128, LSE, F16>(p, splits, stream);
     else
-        launch_dpad<160, F16>(p, stream);
+        launch_dpad<160, LSE, F16>(p, splits, stream);
 }
 
-void launch_flash_attention_d64(const FlashAttnParams& p, int dtype, hipStream_t stream) {
-    if (dtype == DFA_F16)
-        launch_plain<true>(p, stream);
-    else
-        launch_plain<false>(p, stream);
-}
+}  // namespace
 
 int flash_attention_num_splits(int64_t lkv, int splits) {
     const int64_t tiles = (lkv + KVB - 1) / KVB;
     return (int)std::max<int64_t>(1, std::min<int64_t>(splits, tiles));
 }
 
-template <bool F16>
-static void launch_lse(const FlashAttnLseParams& p, int splits, hipStream_t stream) {
-    if (p.Dh <= 64)
-        launch_dpad_lse<64, F16>(p, splits, stream);
-    else if (p.Dh <= 96)
-        launch_dpad_lse<96, F16>(p, splits, stream);
-    else if (p.Dh <= 128)
-        launch_dpad_lse<128, F16>(p, splits, stream);
-    else
-        launch_dpad_lse<160, F16>(p, splits, stream);
-}
-
-void launch_flash_attention_lse(const FlashAttnLseParams& p, int splits, int dtype,
-                                hipStream_t stream) {
-    splits = flash_attention_num_splits(p.NC * p.LC, splits);
-    if (dtype == DFA_F16)
-        launch_lse<true>(p, splits, stream);
-    else
-        launch_lse<false>(p, splits, stream);
+void launch_flash_attention(const FlashAttnLseParams& p, int splits, int dtype,
+                            hipStream_t stream) {
+    const bool f16 = dtype == DFA_F16;
+    if (p.lse == nullptr && p.o_part == nullptr) {
+        (f16 ? launch_ladder<false, true> : launch_ladder<false, false>)(p, 1, stream);
+    } else {
+        splits = flash_attention_num_splits(p.NC * p.LC, splits);
+        (f16 ? launch_ladder<true, true> : launch_ladder<true, false>)(p, splits, stream);
+    }
 }
 
 // ---- fragment-layout probes (tests/test_ops_gpu.py) ------------------------
@@ -747,7 +703,7 @@ __global__ void mfma_probe_kernel(const float* __restrict__ a, const float* __re
         af[j] = __builtin_bit_cast(short, __float2bfloat16(a[lane * 8 + j]));
         bf[j] = __builtin_bit_cast(short, __float2bfloat16(b[lane * 8 + j]));
     }
-    float4v_ acc = {};
+    float4v acc = {};
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf, acc, 0, 0, 0);
 #pragma unroll
     for (int r = 0; r < 4; ++r) d[lane * 4 + r] = acc[r];

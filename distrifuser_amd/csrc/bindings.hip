@@ -6,6 +6,8 @@
 #include <ATen/hip/HIPContext.h>
 #include <c10/hip/HIPStream.h>
 
+#include <array>
+
 #include "kernels.h"
 
 namespace {
@@ -26,6 +28,31 @@ bool is_b16(const at::Tensor& t) {
 
 hipStream_t cur_stream() { return at::hip::getCurrentHIPStream().stream(); }
 
+// A 16-bit parameter of a 16-bit op, in ref's dtype: an fp32 master copy is
+// cast as it always was, the other 16-bit type is a mix-up
+at::Tensor b16_param(const at::Tensor& t, const at::Tensor& ref, const char* op,
+                     const char* name) {
+    TORCH_CHECK(t.scalar_type() == ref.scalar_type() || !is_b16(t), op, ": ", name,
+                " must have x's dtype (", ref.scalar_type(), "), got ", t.scalar_type());
+    return t.to(ref.scalar_type()).contiguous();
+}
+
+// fp32 [2, ngt] sum and sum of squares of x's ngt groups of group_len elements
+at::Tensor gn_partial_stats(const at::Tensor& x, int64_t group_len, int ngt) {
+    auto partial = at::zeros({2, (long)ngt}, x.options().dtype(at::kFloat));
+    launch_gn_stats_partial(x.data_ptr(), partial.data_ptr<float>(), group_len, ngt,
+                            dtype_of(x), cur_stream());
+    return partial;
+}
+
+// Optional GroupNorm affine tensor in x's dtype, contiguous (kept alive in
+// `keep`), or null
+const void* gn_affine(const c10::optional<at::Tensor>& t, const at::Tensor& x, at::Tensor& keep) {
+    if (!t.has_value()) return nullptr;
+    keep = t->to(x.scalar_type()).contiguous();
+    return keep.data_ptr();
+}
+
 at::Tensor group_norm_stats(const at::Tensor& x_, int64_t num_groups) {
     TORCH_CHECK(x_.is_cuda() && x_.dim() == 4, "x must be CUDA [N,C,H,W]");
     auto x = x_.contiguous();
@@ -33,9 +60,7 @@ at::Tensor group_norm_stats(const at::Tensor& x_, int64_t num_groups) {
     TORCH_CHECK(c % num_groups == 0);
     const int64_t group_len = (c / num_groups) * hw;
     const int ngt = (int)(n * num_groups);
-    auto partial = at::zeros({2, (long)ngt}, x.options().dtype(at::kFloat));
-    launch_gn_stats_partial(x.data_ptr(), partial.data_ptr<float>(), group_len, ngt,
-                            dtype_of(x), cur_stream());
+    auto partial = gn_partial_stats(x, group_len, ngt);
     auto out = at::empty({2, n, num_groups, 1, 1, 1}, x.options());
     launch_gn_finalize(partial.data_ptr<float>(), out.data_ptr(), 1.0f / (float)group_len, ngt,
                        dtype_of(x), cur_stream());
@@ -54,16 +79,8 @@ at::Tensor group_norm_apply(const at::Tensor& x_, const at::Tensor& mean_,
     const int g = (int)(mean.numel() / n);
     TORCH_CHECK(c % g == 0, "channels ", c, " not divisible by groups ", g);
     at::Tensor w, b;
-    const void* wp = nullptr;
-    const void* bp = nullptr;
-    if (w_.has_value()) {
-        w = w_->to(x.scalar_type()).contiguous();
-        wp = w.data_ptr();
-    }
-    if (b_.has_value()) {
-        b = b_->to(x.scalar_type()).contiguous();
-        bp = b.data_ptr();
-    }
+    const void* wp = gn_affine(w_, x, w);
+    const void* bp = gn_affine(b_, x, b);
     auto y = at::empty_like(x);
     launch_gn_apply(x.data_ptr(), y.data_ptr(), mean.data_ptr<float>(), meansq.data_ptr<float>(),
                     wp, bp, (float)eps, hw, (int)c, g, (int)n, silu, dtype_of(x), cur_stream());
@@ -79,24 +96,14 @@ at::Tensor group_norm_silu(const at::Tensor& x_, int64_t num_groups,
     TORCH_CHECK(c % num_groups == 0);
     const int64_t group_len = (c / num_groups) * hw;
     const int ngt = (int)(n * num_groups);
-    auto partial = at::zeros({2, (long)ngt}, x.options().dtype(at::kFloat));
-    launch_gn_stats_partial(x.data_ptr(), partial.data_ptr<float>(), group_len, ngt,
-                            dtype_of(x), cur_stream());
+    auto partial = gn_partial_stats(x, group_len, ngt);
     // finalize in fp32 (full precision straight into the apply)
     auto moments = at::empty({2, (long)ngt}, x.options().dtype(at::kFloat));
     launch_gn_finalize(partial.data_ptr<float>(), moments.data_ptr(), 1.0f / (float)group_len,
                        ngt, DFA_F32, cur_stream());
     at::Tensor w, b;
-    const void* wp = nullptr;
-    const void* bp = nullptr;
-    if (w_.has_value()) {
-        w = w_->to(x.scalar_type()).contiguous();
-        wp = w.data_ptr();
-    }
-    if (b_.has_value()) {
-        b = b_->to(x.scalar_type()).contiguous();
-        bp = b.data_ptr();
-    }
+    const void* wp = gn_affine(w_, x, w);
+    const void* bp = gn_affine(b_, x, b);
     auto y = at::empty_like(x);
     launch_gn_apply(x.data_ptr(), y.data_ptr(), moments.data_ptr<float>(),
                     moments.data_ptr<float>() + ngt, wp, bp, (float)eps, hw, (int)c,
@@ -207,33 +214,55 @@ FlashAttnParams flash_params(const at::Tensor& q, const at::Tensor& k, const at:
     return p;
 }
 
-at::Tensor flash_attention(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v) {
-    FlashAttnParams p = flash_params(q, k, v);
+// 16-bit output [B,Lq,H,D] for p, seated in p.o
+at::Tensor flash_out(FlashAttnLseParams& p, const at::Tensor& q) {
     auto o = at::empty({(long)p.B, (long)p.Lq, (long)p.H, (long)p.Dh}, q.options());
     p.o = reinterpret_cast<uint16_t*>(o.data_ptr());
-    launch_flash_attention_d64(p, dtype_of(q), cur_stream());
-    return o.permute({0, 2, 1, 3});  // logical [B,H,Lq,64]
+    return o;
+}
+
+// one split, no log-sum-exp: the plain kernel -> logical [B,H,Lq,D]
+at::Tensor flash_plain(FlashAttnLseParams p, const at::Tensor& q) {
+    auto o = flash_out(p, q);
+    launch_flash_attention(p, 1, dtype_of(q), cur_stream());
+    return o.permute({0, 2, 1, 3});
+}
+
+at::Tensor flash_attention(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v) {
+    return flash_plain({flash_params(q, k, v)}, q);
+}
+
+// A split-KV request: the params, S = the number of splits actually used
+// (kv_splits clamped to the number of 128-token tiles) and the fp32 workspace
+// shapes that go with it, o_part [S,B,Lq,H,D] and lse_part [S,B,H,Lq]
+struct SplitKv {
+    FlashAttnLseParams p;
+    int S;
+    std::array<int64_t, 5> o_part;
+    std::array<int64_t, 4> lse_part;
+};
+SplitKv split_kv(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                 int64_t kv_splits) {
+    TORCH_CHECK(kv_splits >= 1, "kv_splits must be >= 1");
+    const FlashAttnLseParams p{flash_params(q, k, v)};
+    const int S = flash_attention_num_splits(p.NC * p.LC, (int)std::min<int64_t>(kv_splits, 1 << 16));
+    return {p, S, {S, p.B, p.Lq, p.H, p.Dh}, {S, p.B, p.H, p.Lq}};
 }
 
 // Split-KV partials into caller-owned buffers: o_part fp32 [S,B,Lq,H,D] and
-// lse_part fp32 [S,B,H,Lq], S = the number of splits actually used (kv_splits
-// clamped to the number of 128-token tiles), which is returned.
+// lse_part fp32 [S,B,H,Lq]; S is returned.
 int64_t flash_attention_partial(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                                 int64_t kv_splits, at::Tensor o_part, at::Tensor lse_part) {
-    TORCH_CHECK(kv_splits >= 1, "kv_splits must be >= 1");
-    FlashAttnLseParams p{flash_params(q, k, v)};
-    const int S = flash_attention_num_splits(p.NC * p.LC, (int)std::min<int64_t>(kv_splits, 1 << 16));
+    auto [p, S, o_shape, lse_shape] = split_kv(q, k, v, kv_splits);
     TORCH_CHECK(o_part.is_cuda() && o_part.scalar_type() == at::kFloat && o_part.is_contiguous() &&
-                    o_part.sizes() == (at::IntArrayRef{(long)S, (long)p.B, (long)p.Lq, (long)p.H,
-                                                       (long)p.Dh}),
+                    o_part.sizes() == at::IntArrayRef(o_shape),
                 "o_part must be contiguous fp32 [S,B,Lq,H,D] with S = ", S);
     TORCH_CHECK(lse_part.is_cuda() && lse_part.scalar_type() == at::kFloat &&
-                    lse_part.is_contiguous() &&
-                    lse_part.sizes() == (at::IntArrayRef{(long)S, (long)p.B, (long)p.H, (long)p.Lq}),
+                    lse_part.is_contiguous() && lse_part.sizes() == at::IntArrayRef(lse_shape),
                 "lse_part must be contiguous fp32 [S,B,H,Lq] with S = ", S);
     p.o_part = o_part.data_ptr<float>();
     p.lse = lse_part.data_ptr<float>();
-    launch_flash_attention_lse(p, S, dtype_of(q), cur_stream());
+    launch_flash_attention(p, S, dtype_of(q), cur_stream());
     return S;
 }
 
@@ -289,28 +318,22 @@ std::vector<at::Tensor> merge_attention(const at::Tensor& o_parts, const at::Ten
 std::vector<at::Tensor> flash_attention_ext(const at::Tensor& q, const at::Tensor& k,
                                             const at::Tensor& v, int64_t kv_splits,
                                             bool return_lse) {
-    TORCH_CHECK(kv_splits >= 1, "kv_splits must be >= 1");
-    FlashAttnLseParams p{flash_params(q, k, v)};
-    const int S = flash_attention_num_splits(p.NC * p.LC, (int)std::min<int64_t>(kv_splits, 1 << 16));
+    auto [p, S, o_shape, lse_shape] = split_kv(q, k, v, kv_splits);
     const auto f32 = q.options().dtype(at::kFloat);
-    const long B = p.B, H = p.H, Lq = p.Lq, Dh = p.Dh;
+    const long B = p.B, H = p.H, Lq = p.Lq;
     if (S == 1) {
-        auto o = at::empty({B, Lq, H, Dh}, q.options());
-        p.o = reinterpret_cast<uint16_t*>(o.data_ptr());
-        if (!return_lse) {
-            launch_flash_attention_d64(p, dtype_of(q), cur_stream());
-            return {o.permute({0, 2, 1, 3})};
-        }
+        if (!return_lse) return {flash_plain(p, q)};
+        auto o = flash_out(p, q);
         auto lse = at::empty({B, H, Lq}, f32);
         p.lse = lse.data_ptr<float>();
-        launch_flash_attention_lse(p, 1, dtype_of(q), cur_stream());
+        launch_flash_attention(p, 1, dtype_of(q), cur_stream());
         return {o.permute({0, 2, 1, 3}), lse};
     }
-    auto o_part = at::empty({(long)S, B, Lq, H, Dh}, f32);
-    auto lse_part = at::empty({(long)S, B, H, Lq}, f32);
+    auto o_part = at::empty(o_shape, f32);
+    auto lse_part = at::empty(lse_shape, f32);
     p.o_part = o_part.data_ptr<float>();
     p.lse = lse_part.data_ptr<float>();
-    launch_flash_attention_lse(p, S, dtype_of(q), cur_stream());
+    launch_flash_attention(p, S, dtype_of(q), cur_stream());
     // the merge writes the input dtype
     if (!return_lse)
         return {merge_attention_into(o_part, lse_part, q.scalar_type(), c10::nullopt)
@@ -365,9 +388,7 @@ at::Tensor conv3x3(const at::Tensor& x, const at::Tensor& wp,
     if (const char* dbg = getenv("DFA_CONV_DEBUG")) p.debug = atoi(dbg);
     at::Tensor bias_c;
     if (bias.has_value()) {
-        TORCH_CHECK(bias->scalar_type() == dt || !is_b16(*bias),
-                    "conv3x3: bias must have x's dtype (", dt, "), got ", bias->scalar_type());
-        bias_c = bias->to(dt).contiguous();
+        bias_c = b16_param(*bias, x, "conv3x3", "bias");
         TORCH_CHECK(bias_c.numel() == cout);
         p.bias = reinterpret_cast<const uint16_t*>(bias_c.data_ptr());
     }
@@ -387,9 +408,7 @@ at::Tensor conv3x3(const at::Tensor& x, const at::Tensor& wp,
     set_halo(bot, p.bot, p.b_sb, p.b_sc);
     at::Tensor b2_c;
     if (bias2.has_value()) {
-        TORCH_CHECK(bias2->scalar_type() == dt || !is_b16(*bias2),
-                    "conv3x3: bias2 must have x's dtype (", dt, "), got ", bias2->scalar_type());
-        b2_c = bias2->to(dt).contiguous();
+        b2_c = b16_param(*bias2, x, "conv3x3", "bias2");
         TORCH_CHECK(b2_c.numel() == (int64_t)B * cout, "bias2 must be [B, Cout]");
         p.bias2 = reinterpret_cast<const uint16_t*>(b2_c.data_ptr());
     }
@@ -435,22 +454,14 @@ std::vector<at::Tensor> cfg_dpm_step(const at::Tensor& noise, const at::Tensor& 
     return {out, x0};
 }
 
-// LayerNorm affine parameter in x's dtype: an fp32 master copy is cast as it
-// always was, the other 16-bit type is a mix-up
-at::Tensor ln_param(const at::Tensor& t, const at::Tensor& x, const char* op, const char* name) {
-    TORCH_CHECK(t.scalar_type() == x.scalar_type() || !is_b16(t), op, ": ", name,
-                " must have x's dtype (", x.scalar_type(), "), got ", t.scalar_type());
-    return t.to(x.scalar_type()).contiguous();
-}
-
 at::Tensor layer_norm(const at::Tensor& x_, const at::Tensor& w_, const at::Tensor& b_,
                       double eps) {
     TORCH_CHECK(x_.is_cuda() && is_b16(x_), "layer_norm: bf16 or fp16 only");
     auto x = x_.contiguous();
     const int C = (int)x.size(-1);
     TORCH_CHECK(C % 8 == 0 && C <= 2048, "layer_norm kernel: C % 8 == 0 and C <= 2048");
-    auto w = ln_param(w_, x, "layer_norm", "weight");
-    auto b = ln_param(b_, x, "layer_norm", "bias");
+    auto w = b16_param(w_, x, "layer_norm", "weight");
+    auto b = b16_param(b_, x, "layer_norm", "bias");
     auto y = at::empty_like(x);
     launch_layer_norm(x.data_ptr(), nullptr, y.data_ptr(), nullptr, w.data_ptr(), b.data_ptr(),
                       (float)eps, x.numel() / C, C, dtype_of(x), cur_stream());
@@ -467,8 +478,8 @@ std::vector<at::Tensor> add_layer_norm(const at::Tensor& x_, const at::Tensor& r
     TORCH_CHECK(res.sizes() == x.sizes());
     const int C = (int)x.size(-1);
     TORCH_CHECK(C % 8 == 0 && C <= 2048, "add_layer_norm kernel: C % 8 == 0 and C <= 2048");
-    auto w = ln_param(w_, x, "add_layer_norm", "weight");
-    auto b = ln_param(b_, x, "add_layer_norm", "bias");
+    auto w = b16_param(w_, x, "add_layer_norm", "weight");
+    auto b = b16_param(b_, x, "add_layer_norm", "bias");
     auto y = at::empty_like(x);
     auto sum = at::empty_like(x);
     launch_layer_norm(x.data_ptr(), res.data_ptr(), y.data_ptr(), sum.data_ptr(), w.data_ptr(),
@@ -499,15 +510,6 @@ at::Tensor vae_attention(const at::Tensor& q, const at::Tensor& k, const at::Ten
     return o;
 }
 
-std::vector<at::Tensor> mfma_probe(const at::Tensor& a, const at::Tensor& b);
-
-}  // namespace
-
-// defined in attention.hip
-void launch_mfma_probe(const float* a, const float* b, float* d, hipStream_t stream);
-void launch_mfma_probe32(const float* a, const float* b, float* d, hipStream_t stream);
-
-namespace {
 std::vector<at::Tensor> mfma_probe(const at::Tensor& a, const at::Tensor& b) {
     TORCH_CHECK(a.is_cuda() && a.sizes() == (at::IntArrayRef{64, 8}));
     auto af = a.to(at::kFloat).contiguous(), bf = b.to(at::kFloat).contiguous();

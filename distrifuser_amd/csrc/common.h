@@ -31,15 +31,30 @@ __device__ __forceinline__ float from_f32<float>(float v) { return v; }
 // F16 = false: bf16, true: IEEE fp16. A compile-time axis only: the bf16
 // instantiations expand to exactly the code they had before it existed.
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float float16v_ __attribute__((ext_vector_type(16)));
+typedef float float16v __attribute__((ext_vector_type(16)));
 
 template <bool F16>
-__device__ __forceinline__ float16v_ mfma_32x32x16(short8 a, short8 b, float16v_ c) {
+__device__ __forceinline__ float16v mfma_32x32x16(short8 a, short8 b, float16v c) {
     if constexpr (F16)
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8, a),
                                                       __builtin_bit_cast(half8, b), c, 0, 0, 0);
     else
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+
+// 32x32 MFMA D fragment: register r of a lane in half hi = lane >> 5 holds
+// row (r&3) + 8*(r>>2) + 4*hi of column lane & 31
+__device__ __forceinline__ int mfma32_row(int r, int hi) {
+    return (r & 3) + 8 * (r >> 2) + 4 * hi;
+}
+
+// One short8 MFMA operand from LDS rows that are 8 B- but not 16 B-aligned
+// (the 8 B row padding): two b64 reads.
+__device__ __forceinline__ short8 lds_frag_b64x2(const char* addr) {
+    const uint2 a = *reinterpret_cast<const uint2*>(addr);
+    const uint2 b = *reinterpret_cast<const uint2*>(addr + 8);
+    const uint4 v{a.x, a.y, b.x, b.y};
+    return __builtin_bit_cast(short8, v);
 }
 
 // fp32 -> 16 bits, round to nearest even; fp16 overflows to inf (no saturation)
@@ -49,6 +64,13 @@ __device__ __forceinline__ uint16_t f32_to_b16(float v) {
         return __builtin_bit_cast(uint16_t, __float2half(v));
     else
         return __builtin_bit_cast(uint16_t, __float2bfloat16(v));
+}
+// two fp32 -> one dword of two 16-bit values, the first in the low half
+template <bool F16>
+__device__ __forceinline__ uint32_t pack2_b16(float lo, float hi) {
+    const uint32_t e0 = f32_to_b16<F16>(lo);
+    const uint32_t e1 = f32_to_b16<F16>(hi);
+    return e0 | (e1 << 16);
 }
 template <bool F16>
 __device__ __forceinline__ float b16_to_f32(uint16_t v) {
@@ -101,7 +123,8 @@ __device__ __forceinline__ float geluf(float x) {
     return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f));
 }
 
-// In-register 8x8 bf16 transpose across an 8-lane group (butterfly): group
+// In-register 8x8 transpose of 16-bit words (bf16 or fp16: the butterfly
+// never looks inside them) across an 8-lane group (butterfly): group
 // member r = (lane&3)|((lane&8)>>1) holds row r (8 elements = one uint4);
 // afterwards member r holds column r. Lane-mask set {1,2,8} is chosen so
 // every exchange is a VALU DPP op (quad_perm for ^1/^2, row_ror:8 for ^8)
@@ -120,9 +143,9 @@ __device__ __forceinline__ uint32_t dpp_xor8(uint32_t v) {
     return __builtin_amdgcn_mov_dpp(v, 0x128, 0xf, 0xf, true);  // row_ror:8
 }
 
-__device__ __forceinline__ uint4 transpose8x8_bf16(uint4 v, int lane) {
+__device__ __forceinline__ uint4 transpose8x8_b16(uint4 v, int lane) {
     uint32_t d[4] = {v.x, v.y, v.z, v.w};
-    // stage (m=1, e=1): bf16 halves within dwords
+    // stage (m=1, e=1): 16-bit halves within dwords
     {
         const bool hi = (lane & 1) != 0;
 #pragma unroll
@@ -165,11 +188,6 @@ __device__ __forceinline__ uint4 transpose8x8_bf16(uint4 v, int lane) {
     }
     return uint4{d[0], d[1], d[2], d[3]};
 }
-// the butterfly moves 16-bit words and never looks inside them: fp16 rides it
-__device__ __forceinline__ uint4 transpose8x8_b16(uint4 v, int lane) {
-    return transpose8x8_bf16(v, lane);
-}
-
 
 #define DFA_HIP_CHECK(expr)                                                     \
     do {                                                                        \

@@ -35,7 +35,6 @@
 
 namespace {
 
-typedef float float16v __attribute__((ext_vector_type(16)));
 typedef int int32x4_ck __attribute__((ext_vector_type(4)));
 
 // raw-buffer load with hardware bounds check (OOB -> 0); gfx9 descriptor
@@ -54,11 +53,49 @@ __device__ __forceinline__ int32x4_ck make_srsrc(const void* base, uint32_t byte
     return r;
 }
 
+// A tile configuration. S: conv stride; (YB rows) x (XW*32*PW x) output tile
+// per block; CIN_T cins per staged LDS tile; each wave owns PW 32-x subtiles x
+// NCT 32-cout tiles (A fragments reused across the PW subtiles, B across the
+// NCT tiles).
+template <int S_, int YB_, int XW_, int CIN_T_, int NCT_, int PW_>
+struct ConvTile {
+    static constexpr int S = S_, YB = YB_, XW = XW_, CIN_T = CIN_T_, NCT = NCT_, PW = PW_;
+    static constexpr int NW = YB * XW;       // waves per block
+    static constexpr int XB = XW * 32 * PW;  // output x per block
+};
+// stride 1, wide: 8 waves: 8 output rows x 1 x-wave of 64 px (PW=2 A-frag
+// reuse), 128 couts per block (NCT=4 halves the input re-read);
+// LDS (double-buffered): 2 x (input 10x66x40 B + 36 KB weight frags).
+using ConvWideS1 = ConvTile<1, 8, 1, 16, 4, 2>;
+// stride 1, Wo <= 128 (SDXL's 120^2 mid/up shapes): 32-px tiles at
+// 127 VGPRs / 64 KB LDS -> 4 waves/SIMD, 2 blocks/CU; measured +5% over the
+// wide config at 1280@120^2 (the wide config's 64-px tiles also waste 6% on
+// the 120->128 x-pad there)
+using ConvNarrowS1 = ConvTile<1, 8, 1, 16, 2, 1>;
+// stride 2: 8 waves: 4 output rows x 2 x-waves of 32 px;
+// LDS (double-buffered): 2 x (parity input 46.8 KB + 18.4 KB weights).
+using ConvS2 = ConvTile<2, 4, 2, 16, 2, 1>;
 
-// S: conv stride; (YB rows) x (XW*32*PW x) output tile per block; CIN_T cins
-// per staged LDS tile; each wave owns PW 32-x subtiles x NCT 32-cout tiles
-// (A fragments reused across the PW subtiles, B across the NCT tiles).
-//
+// The 1-D grid of a configuration: nxb x nyb pixel-tiles per image, npix of
+// them over the batch, ncb cout-blocks each; `blocks` pads npix to a multiple
+// of 8 for the kernel's XCD-aware decode. The launcher and the kernel's block
+// decode both take it from here.
+struct ConvGrid {
+    int nxb, nyb, npix, ncb;
+    unsigned blocks;
+};
+template <class T>
+__host__ __device__ __forceinline__ ConvGrid conv_grid(const Conv3x3Params& p) {
+    ConvGrid g;
+    g.nxb = (p.Wo + T::XB - 1) / T::XB;
+    g.nyb = (p.Ho + T::YB - 1) / T::YB;
+    g.npix = g.nxb * g.nyb * p.B;  // pixel-tiles x batch
+    g.ncb = (p.CT + T::NCT - 1) / T::NCT;
+    g.blocks = (unsigned)(8 * g.ncb * ((g.npix + 7) / 8));
+    return g;
+}
+
+// T: the tile configuration.
 // Measured evolution (kernel_bench, 1280x1280@120^2, see profiles/):
 //   v1 scalar-gather staging ............ 120 TF (vmem instr bound)
 //   v3 LDS-staged weights + PW=2 ........ 385 TF (A-frag L2 latency fixed)
@@ -77,11 +114,11 @@ __device__ __forceinline__ int32x4_ck make_srsrc(const void* base, uint32_t byte
 // reads shift one column right (xi = 2x + dx + 1), and the scalar column pass
 // stages xi = XIN (x = xb0*S + 2*XB, plane 1 row XB) instead of the left halo
 // xi = 0, which this mode never reads.
-template <int S, int YB, int XW, int CIN_T, int NCT, int PW, bool F16 = false, int PL = 1>
-__global__ __launch_bounds__(YB * XW * WAVE_SIZE) void conv3x3_kernel(Conv3x3Params p) {
+template <class T, bool F16, int PL>
+__global__ __launch_bounds__(T::NW * WAVE_SIZE) void conv3x3_kernel(Conv3x3Params p) {
+    constexpr int S = T::S, YB = T::YB, XW = T::XW, CIN_T = T::CIN_T, NCT = T::NCT, PW = T::PW;
+    constexpr int NW = T::NW, XB = T::XB;
     static_assert(PL == 1 || (PL == 0 && S == 2), "pad_lo = 0 is the stride-2 downsample only");
-    constexpr int NW = YB * XW;
-    constexpr int XB = XW * 32 * PW;
     constexpr int YIN = (YB - 1) * S + 3;          // staged input rows
     constexpr int XIN = (XB - 1) * S + 3;          // staged input x positions
     constexpr int XP = (S == 1) ? XIN : (XB + 1);  // rows per x-parity plane
@@ -110,10 +147,8 @@ __global__ __launch_bounds__(YB * XW * WAVE_SIZE) void conv3x3_kernel(Conv3x3Par
     // input tile and the cout-block's weights then live in that XCD's L2.
     // (Without this, PMC showed every staged byte fetched from HBM:
     // TCC_EA_RDREQ == staged volume, 1.45 GB/dispatch at 1280^2@120^2.)
-    const int nxb = (p.Wo + XB - 1) / XB;
-    const int nyb = (p.Ho + YB - 1) / YB;
-    const int npix = nxb * nyb * p.B;  // pixel-tiles x batch
-    const int ncb = (p.CT + NCT - 1) / NCT;
+    const ConvGrid g = conv_grid<T>(p);
+    const int nxb = g.nxb, nyb = g.nyb, npix = g.npix, ncb = g.ncb;
     const int D = blockIdx.x;
     const int cb = (D >> 3) % ncb;
     const int pp = (D & 7) + 8 * ((D >> 3) / ncb);
@@ -338,12 +373,8 @@ __global__ __launch_bounds__(YB * XW * WAVE_SIZE) void conv3x3_kernel(Conv3x3Par
                         const int xi = ((wx * PW + px) * 32 + lo) * S + dx + (1 - PL);
                         const int plane = (S == 1) ? 0 : (xi & 1);
                         const int row = (S == 1) ? xi : (xi >> 1);
-                        const char* baddr = &inb[((plane * YIN + ry) * XP + row) * ROW_P +
-                                                    (ks2 * 16 + hi * 8) * 2];
-                        const uint2 b0 = *reinterpret_cast<const uint2*>(baddr);
-                        const uint2 b1 = *reinterpret_cast<const uint2*>(baddr + 8);
-                        const uint4 bb{b0.x, b0.y, b1.x, b1.y};
-                        bfrag[px] = __builtin_bit_cast(short8, bb);
+                        bfrag[px] = lds_frag_b64x2(&inb[((plane * YIN + ry) * XP + row) * ROW_P +
+                                                        (ks2 * 16 + hi * 8) * 2]);
                     }
 #pragma unroll
                     for (int ct2 = 0; ct2 < NCT; ++ct2) {
@@ -394,7 +425,7 @@ __global__ __launch_bounds__(YB * XW * WAVE_SIZE) void conv3x3_kernel(Conv3x3Par
             if (ct >= p.CT) break;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int cout = ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                const int cout = ct * 32 + mfma32_row(r, hi);
                 if (cout < p.Cout) {
                     float v = acc[ct2][px][r];
                     if (p.bias) v += b16_to_f32<F16>(p.bias[cout]);
@@ -408,57 +439,27 @@ __global__ __launch_bounds__(YB * XW * WAVE_SIZE) void conv3x3_kernel(Conv3x3Par
     }
 }
 
-}  // namespace
+template <class T, bool F16, int PL = 1>
+void launch_tile(const Conv3x3Params& p, hipStream_t stream) {
+    conv3x3_kernel<T, F16, PL>
+        <<<dim3(conv_grid<T>(p).blocks), dim3(T::NW * WAVE_SIZE), 0, stream>>>(p);
+}
 
 template <bool F16>
-static void launch_conv3x3_t(const Conv3x3Params& p, int stride, hipStream_t stream) {
-    if (stride == 1) {
-        // 8 waves: 8 output rows x 1 x-wave of 64 px (PW=2 A-frag reuse),
-        // 128 couts per block (NCT=4 halves the input re-read);
-        // LDS (double-buffered): 2 x (input 10x66x40 B + 36 KB weight frags).
-        constexpr int YB = 8, XW = 1, NCT = 4, PW = 2;
-        constexpr int XB = XW * 32 * PW;
-        const int nxb = (p.Wo + XB - 1) / XB;
-        const int nyb = (p.Ho + YB - 1) / YB;
-        const int npix = nxb * nyb * p.B;
-        const int ncb = (p.CT + NCT - 1) / NCT;
-        dim3 grid((unsigned)(8 * ncb * ((npix + 7) / 8)));
-        if (p.Wo <= 128) {
-            // small-W config (SDXL's 120^2 mid/up shapes): 32-px tiles at
-            // 127 VGPRs / 64 KB LDS -> 4 waves/SIMD, 2 blocks/CU; measured
-            // +5% over the wide config at 1280@120^2 (the wide config's
-            // 64-px tiles also waste 6% on the 120->128 x-pad there)
-            constexpr int YB2 = 8, XW2 = 1, NCT2 = 2, PW2 = 1;
-            constexpr int XB2 = XW2 * 32 * PW2;
-            const int nxb2 = (p.Wo + XB2 - 1) / XB2;
-            const int nyb2 = (p.Ho + YB2 - 1) / YB2;
-            const int npix2 = nxb2 * nyb2 * p.B;
-            const int ncb2 = (p.CT + NCT2 - 1) / NCT2;
-            dim3 g2((unsigned)(8 * ncb2 * ((npix2 + 7) / 8)));
-            conv3x3_kernel<1, YB2, XW2, 16, NCT2, PW2, F16>
-                <<<g2, dim3(YB2 * XW2 * WAVE_SIZE), 0, stream>>>(p);
-            return;
-        }
-        conv3x3_kernel<1, YB, XW, 16, NCT, PW, F16>
-            <<<grid, dim3(YB * XW * WAVE_SIZE), 0, stream>>>(p);
-    } else {
-        // stride 2: 8 waves: 4 output rows x 2 x-waves of 32 px;
-        // LDS (double-buffered): 2 x (parity input 46.8 KB + 18.4 KB weights).
-        constexpr int YB = 4, XW = 2, NCT = 2, PW = 1;
-        constexpr int XB = XW * 32 * PW;
-        const int nxb = (p.Wo + XB - 1) / XB;
-        const int nyb = (p.Ho + YB - 1) / YB;
-        const int npix = nxb * nyb * p.B;
-        const int ncb = (p.CT + NCT - 1) / NCT;
-        dim3 grid((unsigned)(8 * ncb * ((npix + 7) / 8)));
+void launch_conv3x3_t(const Conv3x3Params& p, int stride, hipStream_t stream) {
+    if (stride != 1) {
         if (p.pad_lo == 0)
-            conv3x3_kernel<2, YB, XW, 16, NCT, PW, F16, 0>
-                <<<grid, dim3(YB * XW * WAVE_SIZE), 0, stream>>>(p);
+            launch_tile<ConvS2, F16, 0>(p, stream);
         else
-            conv3x3_kernel<2, YB, XW, 16, NCT, PW, F16>
-                <<<grid, dim3(YB * XW * WAVE_SIZE), 0, stream>>>(p);
+            launch_tile<ConvS2, F16>(p, stream);
+    } else if (p.Wo <= 128) {
+        launch_tile<ConvNarrowS1, F16>(p, stream);
+    } else {
+        launch_tile<ConvWideS1, F16>(p, stream);
     }
 }
+
+}  // namespace
 
 void launch_conv3x3(const Conv3x3Params& p, int stride, int dtype, hipStream_t stream) {
     if (dtype == DFA_F16)

@@ -115,9 +115,6 @@ struct FlashAttnParams {
     int64_t v_sb, v_sh, v_sc, v_sl;
     float scale;  // 1/sqrt(64)
 };
-// dtype: DFA_BF16 or DFA_F16, the element type of q/k/v/o (the caller rejects
-// DFA_F32); a template axis of the kernel, the parameter block is the same.
-void launch_flash_attention_d64(const FlashAttnParams& p, int dtype, hipStream_t stream);
 
 // LSE / split-KV mode of the same kernel. lse: fp32 [S, B, H, Lq], the natural
 // log of each row's sum of exp(scale * q.k) over the split's KV slice (-inf
@@ -131,8 +128,16 @@ struct FlashAttnLseParams : FlashAttnParams {
 // S the launcher uses for a request of `splits`: clamped to [1, ceil(Lkv/128)]
 // (splits are tile-aligned and never empty).
 int flash_attention_num_splits(int64_t lkv, int splits);
-void launch_flash_attention_lse(const FlashAttnLseParams& p, int splits, int dtype,
-                                hipStream_t stream);
+// lse == null and o_part == null: the plain kernel (one split, `splits` is not
+// read); otherwise the LSE kernel over the clamped number of splits.
+// dtype: DFA_BF16 or DFA_F16, the element type of q/k/v/o (the caller rejects
+// DFA_F32); a template axis of the kernel, the parameter block is the same.
+void launch_flash_attention(const FlashAttnLseParams& p, int splits, int dtype,
+                            hipStream_t stream);
+
+// ---- fragment-layout probes: one wave, a/b fp32 [64][8], d fp32 [64][4] / [64][16] ----
+void launch_mfma_probe(const float* a, const float* b, float* d, hipStream_t stream);
+void launch_mfma_probe32(const float* a, const float* b, float* d, hipStream_t stream);
 
 // ---- merge of attention partials ----------------------------------------------
 // out[b,q,h,:] = sum_s w_s o_parts[s,b,q,h,:] / sum_s w_s, w_s = exp(lse_s - max_s lse_s);

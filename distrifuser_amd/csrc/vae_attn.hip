@@ -27,8 +27,6 @@
 
 namespace {
 
-typedef float float16v __attribute__((ext_vector_type(16)));
-
 constexpr int NW = 4;        // waves = d-slices
 constexpr int QT = 32;       // queries per block
 constexpr int KVB = 32;      // kv tokens per tile
@@ -41,13 +39,6 @@ constexpr int K_ROW = C * 2 + 8;    // k_lds row bytes [t][d]
 constexpr int VT_ROW = KVB * 2 + 8; // vt_lds row bytes [d][t]
 constexpr int P_ROW = KVB * 2 + 8;  // p_lds row bytes [q][t]
 constexpr int O_ROW = C * 2 + 8;    // o_lds row bytes [q][d] (aliases k_lds)
-
-__device__ __forceinline__ short8 lds_frag_b64x2(const char* addr) {
-    const uint2 a = *reinterpret_cast<const uint2*>(addr);
-    const uint2 b = *reinterpret_cast<const uint2*>(addr + 8);
-    const uint4 v{a.x, a.y, b.x, b.y};
-    return __builtin_bit_cast(short8, v);
-}
 
 // F16: q/k/v/o, the P tile and the O staging are IEEE fp16 instead of bf16
 template <bool F16>
@@ -145,12 +136,9 @@ __global__ __launch_bounds__(NW * WAVE_SIZE) void vae_attn_kernel(VaeAttnParams 
             s = mfma_32x32x16<F16>(kf, qf[ks], s);
         }
         __builtin_amdgcn_s_setprio(0);
-        // lane holds S^T rows t = (r&3)+8*(r>>2)+4*hi for q col lo
+        // lane holds S^T rows t = mfma32_row(r, hi) for q col lo
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int t = (r & 3) + 8 * (r >> 2) + 4 * hi;
-            atomicAdd(&s_red[t][lo], s[r]);
-        }
+        for (int r = 0; r < 16; ++r) atomicAdd(&s_red[mfma32_row(r, hi)][lo], s[r]);
         __syncthreads();
 
         // ---- split-K reduce + shared online softmax -----------------------
@@ -230,7 +218,7 @@ __global__ __launch_bounds__(NW * WAVE_SIZE) void vae_attn_kernel(VaeAttnParams 
         for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int d = wave * DSL + dt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                const int d = wave * DSL + dt * 32 + mfma32_row(r, hi);
                 const float inv = l_lds[lo] > 0.f ? 1.f / l_lds[lo] : 0.f;
                 reinterpret_cast<uint16_t*>(&o_lds[lo * O_ROW])[d] =
                     f32_to_b16<F16>(ot[dt][r] * inv);

@@ -16,7 +16,7 @@ import torch
 from torch import nn
 
 from .. import ops
-from ..ops import NativeConv2d
+from ..ops import NativeConv2d, PlainGroupNorm  # noqa: F401  (PlainGroupNorm re-exported)
 from ..parallel.patch_ops import (
     CachedCrossAttention,
     PatchConv2d,
@@ -25,19 +25,6 @@ from ..parallel.patch_ops import (
 )
 from ..parallel.state import ParallelState
 from ..parallel.tensor_ops import TPAttention, TPConv2d, TPFeedForward
-
-
-class PlainGroupNorm(nn.GroupNorm):
-    """GroupNorm with optionally fused SiLU, routed through ops (HIP kernel)."""
-
-    def __init__(self, num_groups, num_channels, eps=1e-5, affine=True, fuse_silu=False):
-        super().__init__(num_groups, num_channels, eps=eps, affine=affine)
-        self.fuse_silu = fuse_silu
-
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return ops.group_norm_silu(
-            x, self.num_groups, self.weight, self.bias, self.eps, silu=self.fuse_silu
-        )
 
 
 class PlainSelfAttention(nn.Module):

@@ -22,7 +22,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from ..ops import NativeConv2d
+from ..ops import NativeConv2d, PlainGroupNorm
 
 from .. import ops
 
@@ -54,19 +54,16 @@ class VAEResnetBlock(nn.Module):
 
     def __init__(self, in_ch: int, out_ch: int, groups: int):
         super().__init__()
-        self.norm1 = nn.GroupNorm(groups, in_ch, eps=1e-6)
+        self.norm1 = PlainGroupNorm(groups, in_ch, eps=1e-6, fuse_silu=True)
         self.conv1 = NativeConv2d(in_ch, out_ch, 3, padding=1)
-        self.norm2 = nn.GroupNorm(groups, out_ch, eps=1e-6)
+        self.norm2 = PlainGroupNorm(groups, out_ch, eps=1e-6, fuse_silu=True)
         self.conv2 = NativeConv2d(out_ch, out_ch, 3, padding=1)
         self.conv_shortcut = NativeConv2d(in_ch, out_ch, 1) if in_ch != out_ch else None
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        h = self.conv1(ops.group_norm_silu(x, self.norm1.num_groups, self.norm1.weight,
-                                           self.norm1.bias, self.norm1.eps))
+        h = self.conv1(self.norm1(x))
         res = self.conv_shortcut(x) if self.conv_shortcut is not None else x
-        return self.conv2(ops.group_norm_silu(h, self.norm2.num_groups, self.norm2.weight,
-                                              self.norm2.bias, self.norm2.eps),
-                          residual=res)
+        return self.conv2(self.norm2(h), residual=res)
 
 
 def _chunked_single_head_attention(
@@ -103,7 +100,7 @@ class VAEAttention(nn.Module):
 
     def __init__(self, channels: int, groups: int):
         super().__init__()
-        self.group_norm = nn.GroupNorm(groups, channels, eps=1e-6)
+        self.group_norm = PlainGroupNorm(groups, channels, eps=1e-6, fuse_silu=False)
         self.to_q = nn.Linear(channels, channels)
         self.to_k = nn.Linear(channels, channels)
         self.to_v = nn.Linear(channels, channels)
@@ -112,8 +109,7 @@ class VAEAttention(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         b, c, h, w = x.shape
         residual = x
-        x = ops.group_norm_silu(x, self.group_norm.num_groups, self.group_norm.weight,
-                                self.group_norm.bias, self.group_norm.eps, silu=False)
+        x = self.group_norm(x)
         x = x.permute(0, 2, 3, 1).reshape(b, h * w, c)
         q, k, v = self.to_q(x), self.to_k(x), self.to_v(x)
         if x.is_cuda and c == 512 and q.dtype in (torch.bfloat16, torch.float16):
@@ -143,7 +139,90 @@ class UpDecoderBlock2D(nn.Module):
         return x
 
 
-class VAEDecoder(nn.Module):
+@torch.no_grad()
+def _tiled_apply(fn, x: torch.Tensor, tile: int, overlap: int, scale_num: int,
+                 scale_den: int) -> torch.Tensor:
+    """Apply ``fn`` to overlapping ``tile``-sized tiles of ``x`` and linearly
+    blend the seams (diffusers AutoencoderKL tiled decode / encode parity).
+
+    ``tile`` and ``overlap`` are in input pixels; ``fn`` scales both spatial
+    sides by ``scale_num / scale_den`` (x8 for decode, /8 for encode).
+    """
+    def out_px(n):
+        return n * scale_num // scale_den
+
+    stride = tile - overlap
+    b, _, h, w = x.shape
+    ys = list(range(0, max(h - overlap, 1), stride))
+    xs = list(range(0, max(w - overlap, 1), stride))
+    # Full-size tiles run as ONE batched pass (288 GB HBM3E holds all
+    # activations comfortably); ragged edge tiles run individually.
+    tiles = {}
+    full = [(y0, x0) for y0 in ys for x0 in xs
+            if y0 + tile <= h and x0 + tile <= w]
+    if len(full) > 1 and b == 1:
+        batch = torch.cat([x[:, :, y0 : y0 + tile, x0 : x0 + tile]
+                           for (y0, x0) in full])
+        res = fn(batch)
+        for i, key in enumerate(full):
+            tiles[key] = res[i : i + 1]
+    for y0 in ys:
+        for x0 in xs:
+            if (y0, x0) not in tiles:
+                tiles[(y0, x0)] = fn(x[:, :, y0 : y0 + tile, x0 : x0 + tile])
+    rows = [[tiles[(y0, x0)] for x0 in xs] for y0 in ys]
+
+    def blend_v(a, bt, k):
+        k = min(k, a.shape[2], bt.shape[2])
+        w_ = torch.linspace(0, 1, k, device=a.device, dtype=a.dtype).view(1, 1, k, 1)
+        bt[:, :, :k] = a[:, :, a.shape[2] - k :] * (1 - w_) + bt[:, :, :k] * w_
+        return bt
+
+    def blend_h(a, bt, k):
+        k = min(k, a.shape[3], bt.shape[3])
+        w_ = torch.linspace(0, 1, k, device=a.device, dtype=a.dtype).view(1, 1, 1, k)
+        bt[:, :, :, :k] = a[:, :, :, a.shape[3] - k :] * (1 - w_) + bt[:, :, :, :k] * w_
+        return bt
+
+    ov_out, st_out = out_px(overlap), out_px(stride)
+    out_rows = []
+    for i, row in enumerate(rows):
+        parts = []
+        for j, t in enumerate(row):
+            if i > 0:
+                t = blend_v(rows[i - 1][j], t, ov_out)
+            if j > 0:
+                t = blend_h(row[j - 1], t, ov_out)
+            keep_w = st_out if j < len(row) - 1 else t.shape[3]
+            parts.append(t[:, :, :st_out, :keep_w] if i < len(rows) - 1
+                         else t[:, :, :, :keep_w])
+        out_rows.append(torch.cat(parts, dim=3))
+    out = torch.cat(out_rows, dim=2)
+    return out[:, :, : out_px(h), : out_px(w)]
+
+
+class _TilingMixin:
+    """Tiling state shared by the decoder and the encoder. The mid-block
+    attention is O(L^2) in latent tokens: a full 3840^2 decode attends over
+    230k tokens (~109 TFLOP in that one layer). Tiling runs overlapping tiles
+    independently and linearly blends the seams — the standard high-resolution
+    VAE path. Sizes are in latent pixels on both sides, so an encoder tile is
+    tile_latent_size * 8 image pixels."""
+
+    use_tiling: bool = False
+    tile_latent_size: int = 96
+    tile_overlap: int = 16  # latent pixels blended between neighbouring tiles
+
+    def enable_tiling(self, tile_latent_size: int = 96, tile_overlap: int = 16) -> None:
+        self.use_tiling = True
+        self.tile_latent_size = tile_latent_size
+        self.tile_overlap = tile_overlap
+
+    def disable_tiling(self) -> None:
+        self.use_tiling = False
+
+
+class VAEDecoder(_TilingMixin, nn.Module):
     def __init__(self, config: VAEDecoderConfig):
         super().__init__()
         self.config = config
@@ -167,25 +246,8 @@ class VAEDecoder(nn.Module):
             )
             prev = out_ch
         self.up_blocks = nn.ModuleList(blocks)
-        self.conv_norm_out = nn.GroupNorm(groups, ch[0], eps=1e-6)
+        self.conv_norm_out = PlainGroupNorm(groups, ch[0], eps=1e-6, fuse_silu=True)
         self.conv_out = NativeConv2d(ch[0], config.out_channels, 3, padding=1)
-
-    # -- tiled decode (diffusers AutoencoderKL.enable_tiling parity) --------
-    # The mid-block attention is O(L^2) in latent tokens: a full 3840^2
-    # decode attends over 230k tokens (~109 TFLOP in that one layer). Tiling
-    # decodes overlapping latent tiles independently and linearly blends the
-    # seams — the standard high-resolution VAE path.
-    use_tiling: bool = False
-    tile_latent_size: int = 96
-    tile_overlap: int = 16  # latent pixels blended between neighbouring tiles
-
-    def enable_tiling(self, tile_latent_size: int = 96, tile_overlap: int = 16) -> None:
-        self.use_tiling = True
-        self.tile_latent_size = tile_latent_size
-        self.tile_overlap = tile_overlap
-
-    def disable_tiling(self) -> None:
-        self.use_tiling = False
 
     @torch.no_grad()
     def _decode_one(self, z: torch.Tensor) -> torch.Tensor:
@@ -195,64 +257,10 @@ class VAEDecoder(nn.Module):
         x = self.mid_resnet_2(x)
         for block in self.up_blocks:
             x = block(x)
-        x = ops.group_norm_silu(x, self.conv_norm_out.num_groups, self.conv_norm_out.weight,
-                                self.conv_norm_out.bias, self.conv_norm_out.eps)
-        return self.conv_out(x)
+        return self.conv_out(self.conv_norm_out(x))
 
-    @torch.no_grad()
     def _decode_tiled(self, z: torch.Tensor) -> torch.Tensor:
-        ts, ov = self.tile_latent_size, self.tile_overlap
-        stride = ts - ov
-        b, _, h, w = z.shape
-        sf = 8  # spatial upscale of the decoder
-        ys = list(range(0, max(h - ov, 1), stride))
-        xs = list(range(0, max(w - ov, 1), stride))
-        # Full-size tiles decode as ONE batched pass (288 GB HBM3E holds all
-        # activations comfortably); ragged edge tiles decode individually.
-        tiles = {}
-        full = [(y0, x0) for y0 in ys for x0 in xs
-                if y0 + ts <= h and x0 + ts <= w]
-        if len(full) > 1 and b == 1:
-            batch = torch.cat([z[:, :, y0 : y0 + ts, x0 : x0 + ts]
-                               for (y0, x0) in full])
-            dec = self._decode_one(batch)
-            for i, key in enumerate(full):
-                tiles[key] = dec[i : i + 1]
-        for y0 in ys:
-            for x0 in xs:
-                if (y0, x0) not in tiles:
-                    tiles[(y0, x0)] = self._decode_one(
-                        z[:, :, y0 : y0 + ts, x0 : x0 + ts])
-        rows = [[tiles[(y0, x0)] for x0 in xs] for y0 in ys]
-
-        def blend_v(a, bt, k):
-            k = min(k, a.shape[2], bt.shape[2])
-            w_ = torch.linspace(0, 1, k, device=a.device, dtype=a.dtype).view(1, 1, k, 1)
-            bt[:, :, :k] = a[:, :, a.shape[2] - k :] * (1 - w_) + bt[:, :, :k] * w_
-            return bt
-
-        def blend_h(a, bt, k):
-            k = min(k, a.shape[3], bt.shape[3])
-            w_ = torch.linspace(0, 1, k, device=a.device, dtype=a.dtype).view(1, 1, 1, k)
-            bt[:, :, :, :k] = a[:, :, :, a.shape[3] - k :] * (1 - w_) + bt[:, :, :, :k] * w_
-            return bt
-
-        ov_px = ov * sf
-        st_px = stride * sf
-        out_rows = []
-        for i, row in enumerate(rows):
-            parts = []
-            for j, tile in enumerate(row):
-                if i > 0:
-                    tile = blend_v(rows[i - 1][j], tile, ov_px)
-                if j > 0:
-                    tile = blend_h(row[j - 1], tile, ov_px)
-                keep_w = st_px if j < len(row) - 1 else tile.shape[3]
-                parts.append(tile[:, :, :st_px, :keep_w] if i < len(rows) - 1
-                             else tile[:, :, :, :keep_w])
-            out_rows.append(torch.cat(parts, dim=3))
-        out = torch.cat(out_rows, dim=2)
-        return out[:, :, : h * sf, : w * sf]
+        return _tiled_apply(self._decode_one, z, self.tile_latent_size, self.tile_overlap, 8, 1)
 
     @torch.no_grad()
     def decode(self, latents: torch.Tensor) -> torch.Tensor:
@@ -286,7 +294,7 @@ class DownEncoderBlock2D(nn.Module):
         return x
 
 
-class VAEEncoder(nn.Module):
+class VAEEncoder(_TilingMixin, nn.Module):
     """AutoencoderKL encoder: images in [-1, 1] -> posterior moments -> latents.
 
     Built from the decoder's config values and blocks. ``encode`` returns
@@ -320,25 +328,10 @@ class VAEEncoder(nn.Module):
         self.mid_resnet_1 = VAEResnetBlock(top, top, groups)
         self.mid_attn = VAEAttention(top, groups)
         self.mid_resnet_2 = VAEResnetBlock(top, top, groups)
-        self.conv_norm_out = nn.GroupNorm(groups, top, eps=1e-6)
+        self.conv_norm_out = PlainGroupNorm(groups, top, eps=1e-6, fuse_silu=True)
         zc = config.latent_channels * (2 if config.double_z else 1)
         self.conv_out = NativeConv2d(top, zc, 3, padding=1)
         self.quant_conv = NativeConv2d(zc, zc, 1)
-
-    # -- tiled encode (diffusers AutoencoderKL.tiled_encode parity) ---------
-    # Same names and defaults as the decoder; sizes are in latent pixels, so a
-    # tile is tile_latent_size * 8 image pixels.
-    use_tiling: bool = False
-    tile_latent_size: int = 96
-    tile_overlap: int = 16
-
-    def enable_tiling(self, tile_latent_size: int = 96, tile_overlap: int = 16) -> None:
-        self.use_tiling = True
-        self.tile_latent_size = tile_latent_size
-        self.tile_overlap = tile_overlap
-
-    def disable_tiling(self) -> None:
-        self.use_tiling = False
 
     @torch.no_grad()
     def _encode_one(self, x: torch.Tensor) -> torch.Tensor:
@@ -349,64 +342,13 @@ class VAEEncoder(nn.Module):
         x = self.mid_resnet_1(x)
         x = self.mid_attn(x)
         x = self.mid_resnet_2(x)
-        x = ops.group_norm_silu(x, self.conv_norm_out.num_groups, self.conv_norm_out.weight,
-                                self.conv_norm_out.bias, self.conv_norm_out.eps)
-        return self.quant_conv(self.conv_out(x))
+        return self.quant_conv(self.conv_out(self.conv_norm_out(x)))
 
-    @torch.no_grad()
     def _encode_tiled(self, x: torch.Tensor) -> torch.Tensor:
-        sf = self.SPATIAL
-        ts, ov = self.tile_latent_size, self.tile_overlap
-        stride = ts - ov
-        ts_px, ov_px, st_px = ts * sf, ov * sf, stride * sf
-        b, _, h, w = x.shape
-        ys = list(range(0, max(h - ov_px, 1), st_px))
-        xs = list(range(0, max(w - ov_px, 1), st_px))
-        # full-size tiles encode as ONE batched pass, ragged edge tiles one
-        # by one (as the decoder does)
-        tiles = {}
-        full = [(y0, x0) for y0 in ys for x0 in xs
-                if y0 + ts_px <= h and x0 + ts_px <= w]
-        if len(full) > 1 and b == 1:
-            batch = torch.cat([x[:, :, y0 : y0 + ts_px, x0 : x0 + ts_px]
-                               for (y0, x0) in full])
-            enc = self._encode_one(batch)
-            for i, key in enumerate(full):
-                tiles[key] = enc[i : i + 1]
-        for y0 in ys:
-            for x0 in xs:
-                if (y0, x0) not in tiles:
-                    tiles[(y0, x0)] = self._encode_one(
-                        x[:, :, y0 : y0 + ts_px, x0 : x0 + ts_px])
-        rows = [[tiles[(y0, x0)] for x0 in xs] for y0 in ys]
-
         # the MOMENTS are blended, linearly across the overlap, before sampling
-        def blend_v(a, bt, k):
-            k = min(k, a.shape[2], bt.shape[2])
-            w_ = torch.linspace(0, 1, k, device=a.device, dtype=a.dtype).view(1, 1, k, 1)
-            bt[:, :, :k] = a[:, :, a.shape[2] - k :] * (1 - w_) + bt[:, :, :k] * w_
-            return bt
-
-        def blend_h(a, bt, k):
-            k = min(k, a.shape[3], bt.shape[3])
-            w_ = torch.linspace(0, 1, k, device=a.device, dtype=a.dtype).view(1, 1, 1, k)
-            bt[:, :, :, :k] = a[:, :, :, a.shape[3] - k :] * (1 - w_) + bt[:, :, :, :k] * w_
-            return bt
-
-        out_rows = []
-        for i, row in enumerate(rows):
-            parts = []
-            for j, tile in enumerate(row):
-                if i > 0:
-                    tile = blend_v(rows[i - 1][j], tile, ov)
-                if j > 0:
-                    tile = blend_h(row[j - 1], tile, ov)
-                keep_w = stride if j < len(row) - 1 else tile.shape[3]
-                parts.append(tile[:, :, :stride, :keep_w] if i < len(rows) - 1
-                             else tile[:, :, :, :keep_w])
-            out_rows.append(torch.cat(parts, dim=3))
-        out = torch.cat(out_rows, dim=2)
-        return out[:, :, : h // sf, : w // sf]
+        sf = self.SPATIAL
+        return _tiled_apply(self._encode_one, x, self.tile_latent_size * sf,
+                            self.tile_overlap * sf, 1, sf)
 
     @torch.no_grad()
     def encode_moments(self, images: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:

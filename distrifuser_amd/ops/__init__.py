@@ -23,9 +23,11 @@ from .dispatch import (
     merge_attention,
     vae_attention,
 )
+from .norm import PlainGroupNorm
 
 __all__ = [
     "NativeConv2d",
+    "PlainGroupNorm",
     "add_layer_norm",
     "attention_kv_splits",
     "layer_norm",

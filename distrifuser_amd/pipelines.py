@@ -96,6 +96,20 @@ class _DistriPipelineBase:
         self._progress = distri_config.rank == 0 and distri_config.verbose
         self.prepare()
 
+    @staticmethod
+    def _load_components(pretrained, components: dict, device, torch_dtype) -> list:
+        """Load each named component from the checkpoint directory (when one
+        is given), then move it to device / dtype in eval mode. ``components``
+        maps checkpoint subfolder -> module; the modules come back in order."""
+        if pretrained is not None:
+            for comp, model in components.items():
+                path = weight_io.find_component_weights(pretrained, comp)
+                if path is not None:
+                    # the checkpoint holds the plain U-Net inside the DistriUNet wrapper
+                    target = model.unet if isinstance(model, DistriUNet) else model
+                    weight_io.load_into(target, weight_io.load_safetensors(path))
+        return [m.to(device=device, dtype=torch_dtype).eval() for m in components.values()]
+
     # -- reference-API conveniences -----------------------------------------
 
     def set_progress_bar_config(self, disable: bool = False, **kwargs):
@@ -277,6 +291,20 @@ class _DistriPipelineBase:
                     latents = self.scheduler.step(noise, t, latents)
         return latents
 
+    def _generate(self, embeds, added_cond_kwargs, num_inference_steps, guidance_scale,
+                  generator, output_type, image, strength):
+        """The tail both pipelines share once the prompt is encoded: initial
+        (or img2img) latents -> denoise -> decode."""
+        t_start = 0
+        if image is None:
+            latents = self._prepare_latents(1, generator)
+        else:
+            latents, t_start = self._img2img_latents(image, strength, num_inference_steps,
+                                                     generator)
+        latents = self._denoise(latents, embeds, added_cond_kwargs, num_inference_steps,
+                                guidance_scale, t_start)
+        return self._decode(latents, output_type)
+
     def _decode(self, latents: torch.Tensor, output_type: str):
         # High-resolution decode: the VAE mid-attention is O(L^2) in latent
         # tokens, so >= 2048^2 outputs use tiled decode automatically
@@ -402,7 +430,6 @@ class DistriSDXLPipeline(_DistriPipelineBase):
         scheduler = kwargs.pop("scheduler", "ddim")
         preset = kwargs.pop("preset", "sdxl")
         allow_simple = kwargs.pop("allow_simple_tokenizer", False)
-        device = distri_config.device
 
         if preset == "tiny":
             unet_cfg, vae_cfg = TINY_UNET, TINY_VAE
@@ -422,18 +449,9 @@ class DistriSDXLPipeline(_DistriPipelineBase):
         vae = VAEDecoder(vae_cfg)
         te1 = CLIPTextEncoder(clip1_cfg)
         te2 = CLIPTextEncoder(clip2_cfg)
-
-        if pretrained is not None:
-            for model, comp in ((unet.unet, "unet"), (vae, "vae"),
-                                (te1, "text_encoder"), (te2, "text_encoder_2")):
-                path = weight_io.find_component_weights(pretrained, comp)
-                if path is not None:
-                    weight_io.load_into(model, weight_io.load_safetensors(path))
-
-        unet = unet.to(device=device, dtype=torch_dtype).eval()
-        vae = vae.to(device=device, dtype=torch_dtype).eval()
-        te1 = te1.to(device=device, dtype=torch_dtype).eval()
-        te2 = te2.to(device=device, dtype=torch_dtype).eval()
+        unet, vae, te1, te2 = _DistriPipelineBase._load_components(
+            pretrained, {"unet": unet, "vae": vae, "text_encoder": te1, "text_encoder_2": te2},
+            distri_config.device, torch_dtype)
         pipeline = DistriSDXLPipeline(distri_config, unet, vae, te1, te2,
                                       get_scheduler(scheduler), tokenizer,
                                       tokenizer_2=tokenizer_2)
@@ -515,15 +533,8 @@ class DistriSDXLPipeline(_DistriPipelineBase):
         embeds = embeds.to(self._unet_dtype())
         pooled = pooled.to(self._unet_dtype())
         added = self._added_cond(embeds.shape[0], pooled)
-        t_start = 0
-        if image is None:
-            latents = self._prepare_latents(1, generator)
-        else:
-            latents, t_start = self._img2img_latents(image, strength, num_inference_steps,
-                                                     generator)
-        latents = self._denoise(latents, embeds, added, num_inference_steps, guidance_scale,
-                                t_start)
-        return self._decode(latents, output_type)
+        return self._generate(embeds, added, num_inference_steps, guidance_scale, generator,
+                              output_type, image, strength)
 
 
 class DistriSDPipeline(_DistriPipelineBase):
@@ -540,7 +551,6 @@ class DistriSDPipeline(_DistriPipelineBase):
         scheduler = kwargs.pop("scheduler", "ddim")
         preset = kwargs.pop("preset", "sd15")
         allow_simple = kwargs.pop("allow_simple_tokenizer", False)
-        device = distri_config.device
 
         if preset == "tiny":
             unet_cfg = UNetConfig(
@@ -570,15 +580,9 @@ class DistriSDPipeline(_DistriPipelineBase):
         unet = DistriUNet(unet_cfg, distri_config)
         vae = VAEDecoder(vae_cfg)
         te = CLIPTextEncoder(clip_cfg)
-        if pretrained is not None:
-            for model, comp in ((unet.unet, "unet"), (vae, "vae"), (te, "text_encoder")):
-                path = weight_io.find_component_weights(pretrained, comp)
-                if path is not None:
-                    weight_io.load_into(model, weight_io.load_safetensors(path))
-
-        unet = unet.to(device=device, dtype=torch_dtype).eval()
-        vae = vae.to(device=device, dtype=torch_dtype).eval()
-        te = te.to(device=device, dtype=torch_dtype).eval()
+        unet, vae, te = _DistriPipelineBase._load_components(
+            pretrained, {"unet": unet, "vae": vae, "text_encoder": te},
+            distri_config.device, torch_dtype)
         pipeline = DistriSDPipeline(distri_config, unet, vae, te, get_scheduler(scheduler),
                                     tokenizer)
         pipeline._pretrained_path = pretrained  # for the lazily built VAE encoder
@@ -628,12 +632,5 @@ class DistriSDPipeline(_DistriPipelineBase):
             guidance_scale = 1
         do_cfg = cfg.do_classifier_free_guidance
         embeds = self.encode_prompt(prompt, negative_prompt, do_cfg).to(self._unet_dtype())
-        t_start = 0
-        if image is None:
-            latents = self._prepare_latents(1, generator)
-        else:
-            latents, t_start = self._img2img_latents(image, strength, num_inference_steps,
-                                                     generator)
-        latents = self._denoise(latents, embeds, None, num_inference_steps, guidance_scale,
-                                t_start)
-        return self._decode(latents, output_type)
+        return self._generate(embeds, None, num_inference_steps, guidance_scale, generator,
+                              output_type, image, strength)
