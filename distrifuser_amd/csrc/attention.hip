@@ -9,7 +9,8 @@
 //   KV re-read traffic (each KV tile is re-read Lq/QBLK times).
 // * KV streamed in 128-token LDS tiles shared by the waves. K and V are
 //   staged the same way: b128 global loads into a row-major [t][d] image,
-//   zero-filled beyond Dh and beyond Lkv. K rows are padded by 8 B; V rows
+//   zero-filled beyond Dh and beyond Lkv. K rows are padded by 8 B (XOR-
+//   swizzled instead where the tile is filled by LDS-DMA, below); V rows
 //   are unpadded with a 64 B-granular XOR (v_swz) that keeps the transposed
 //   reads conflict-free.
 // * Full 128-token tiles run mask-free; one peeled tail tile handles
@@ -38,7 +39,22 @@
 //   Any other tile — one that straddles chunk boundaries, the tail, the
 //   other head dims — has every token row resolve its own chunk from the
 //   cursor; the tile loop holds no division either way.
-// * SPLIT staging (guide T14): the next tile's global loads are issued into
+// * Staging, head_dim 64 with all columns real (the SDXL kernels): LDS-DMA
+//   into TWO KV buffers, ONE barrier per tile. A full tile inside one chunk is
+//   fetched by four buffer_load_dwordx4 ... lds per wave (1 KiB each, lane-
+//   linear in LDS) from the tile cursor into the buffer the previous tile was
+//   read from: no staging registers, no ds_write. Per tile: vmcnt(0) for the
+//   wave's own DMA, s_barrier (tile t visible, every wave done with tile
+//   t-1), issue tile t+1, compute tile t. The LDS image is made on the source
+//   side: each lane fetches the 16 B column whose swizzled place is its
+//   linear slot. K rows are unpadded 128 B under a 16 B-window XOR
+//   ((t >> 1) & 7) and read with one ds_read_b128 per fragment; V keeps
+//   v_swz. A tile that straddles chunks and the tail go through registers
+//   after the compute (load, ds_write into the other buffer) and are
+//   published by the same barrier, so the two kinds alternate freely.
+//   (profiles/attention_dma_notes.md)
+// * SPLIT staging (guide T14), every other instantiation: one KV buffer; the
+//   next tile's global loads are issued into
 //   registers before the current tile's compute and written to LDS after the
 //   barrier that ends it; the barriers are raw s_barrier + lgkmcnt-only
 //   waits, so the loads stay in flight across them.
@@ -67,8 +83,8 @@ namespace {
 constexpr int QW = 32;     // q rows per wave
 constexpr int KVB = 128;   // kv tokens per LDS tile
 // split staging (issue-early / write-late) measured +1 % at L=57.6k and
-// +5-7 % on the chunked shapes against loading after the barrier; the kernel
-// has no other mode.
+// +5-7 % on the chunked shapes against loading after the barrier; the
+// register-staged instantiations have no other mode.
 // waves per block is a template parameter: bigger Q blocks amortize the KV
 // stream (each KV tile is re-read Lq/QBLK times), smaller blocks keep small
 // Lq shapes filled. Measured: 4w->8w at L=57.6k was +53% (439->673 TF).
@@ -79,6 +95,12 @@ constexpr int KVB = 128;   // kv tokens per LDS tile
 
 typedef short short4v __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) short4v lds_short4v;
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// byte address of a __shared__ object inside the block's LDS
+__device__ __forceinline__ uint32_t lds_addr(const void* p) {
+    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
+}
 
 template <int DPAD>
 __device__ __forceinline__ int v_swz(int t) {
@@ -155,15 +177,25 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
     // 4-way floor of XOR-swizzled 128 B rows — same trick as the conv
     // kernel's staged tile (profiles/conv_ladder_r02.md v5). Reads/writes
     // are b64 pairs (rows are 8 B- but not 16 B-aligned).
-    constexpr int K_ROW = DPAD * 2 + 8;     // padded K LDS row bytes [t][d]
+    //
+    // DMA instantiations (head_dim 64, all columns real) fill the tile by
+    // LDS-DMA instead, one wave-instruction = 1 KiB = eight rows written
+    // lane-linearly, so their K rows are unpadded 128 B rows under a
+    // 16 B-window XOR (k_swz) applied on the SOURCE side, read back with one
+    // ds_read_b128 per fragment, and both images exist twice.
+    constexpr bool DMA = DFULL && DPAD == 64;
+    constexpr int K_ROW = DMA ? DPAD * 2 : DPAD * 2 + 8;  // K LDS row bytes [t][d]
     constexpr int V_ROW = DPAD * 2;         // V LDS row bytes [t][d], v_swz'd
+    constexpr int K_BYTES = KVB * K_ROW;    // one K image
+    constexpr int V_BYTES = KVB * V_ROW;    // one V image
+    constexpr int NBUF = DMA ? 2 : 1;
     constexpr int KS = DPAD / 16;           // QK^T k-slices
     constexpr int DT = DPAD / 32;           // PV / O^T d-tiles
     constexpr int KCOLS = DPAD / 8;         // 16 B pieces per K/V row
     constexpr int NLD = KVB * KCOLS / NT;   // b128 loads per thread per tile, K and V each
     static_assert(KVB * KCOLS % NT == 0);
-    __shared__ __attribute__((aligned(16))) char k_lds[KVB * K_ROW];
-    __shared__ __attribute__((aligned(16))) char v_lds[KVB * V_ROW];
+    __shared__ __attribute__((aligned(16))) char k_lds[NBUF * K_BYTES];
+    __shared__ __attribute__((aligned(16))) char v_lds[NBUF * V_BYTES];
 
     const int tid = threadIdx.x;
     const int wave = tid / WAVE_SIZE;
@@ -216,6 +248,20 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
             vrd[dt] = (hi * 8 + q) * V_ROW + ((dt * 64 + col_b) ^ v_swz<DPAD>(q));
     }
 
+    // ---- DMA K image: 16 B window w of row t sits at window w ^ k_swz(t).
+    // Even and odd rows fall in the two halves of the 256 B bank row and
+    // (t >> 1) & 7 spreads the 16 rows of a ds_read_b128 lane group over the 8
+    // windows of each half: conflict-free. A sub-tile step is 32 rows, which
+    // leaves k_swz alone, so the fragment addresses are these per-lane bases
+    // plus immediates. krd/vrd also carry the offset of the buffer being read
+    // and flip with it after every tile. ----
+    auto k_swz = [](int t) { return (t >> 1) & 7; };
+    int krd[DMA ? KS : 1];
+    if constexpr (DMA) {
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) krd[ks] = lo * K_ROW + (((ks * 2 + hi) ^ k_swz(lo)) << 4);
+    }
+
     // ---- staging: thread (t-row, 16 B column) moves one b128 piece of K and
     // one of V per pass. cur_chunk/cur_tin locate the first token of the tile
     // being loaded and kcur/vcur point at it; all four are wave-uniform and
@@ -264,8 +310,20 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
     // tile's span fits); the later pieces add the uniform k_pass/v_pass. Only
     // whole-row passes (DPAD 64 and 128) have that form: the others would
     // hold NLD lane offsets per tensor, which DPAD 160 has no registers for.
-    const uint32_t koff = (uint32_t)stage_row(0) * ((uint32_t)p.k_sl * 2) + stage_col(0) * 16;
-    const uint32_t voff = (uint32_t)stage_row(0) * ((uint32_t)p.v_sl * 2) + stage_col(0) * 16;
+    //
+    // DMA instantiations: thread tid owns the linear 16 B slot tid + i*NT of
+    // each image — where its wave's LDS-DMA puts lane data, and where the
+    // register path writes — and fetches the source column whose swizzled
+    // place that slot is. A pass is 64 rows, which changes neither XOR, so the
+    // source column is the same for every pass.
+    auto stage_kcol = [&](int i) {
+        return DMA ? stage_col(i) ^ k_swz(stage_row(i)) : stage_col(i);
+    };
+    auto stage_vcol = [&](int i) {
+        return DMA ? stage_col(i) ^ (v_swz<DPAD>(stage_row(i)) >> 4) : stage_col(i);
+    };
+    const uint32_t koff = (uint32_t)stage_row(0) * ((uint32_t)p.k_sl * 2) + stage_kcol(0) * 16;
+    const uint32_t voff = (uint32_t)stage_row(0) * ((uint32_t)p.v_sl * 2) + stage_vcol(0) * 16;
     const int k_pass = (NT / KCOLS) * (int)p.k_sl * 2;
     const int v_pass = (NT / KCOLS) * (int)p.v_sl * 2;
     // raw buffer descriptor at the (uniform) tile cursor: the load is base in
@@ -275,9 +333,28 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
         return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(cur), 0, 0xFFFFFFFFu,
                                                  0x00020000);
     };
-    // `full`: every token of the tile is below Lkv (all tiles but the tail)
+    // the cursor moves on by one tile
+    auto advance_cursor = [&]() {
+        cur_tin += KVB;
+        kcur += KVB * p.k_sl * 2;
+        vcur += KVB * p.v_sl * 2;
+        if (cur_tin >= LC) {  // chunk crossing: re-seat the cursor
+            do {
+                cur_tin -= LC;
+                ++cur_chunk;
+            } while (cur_tin >= LC);
+            kcur = reinterpret_cast<const char*>(kbase + cur_chunk * p.k_sc + cur_tin * p.k_sl);
+            vcur = reinterpret_cast<const char*>(vbase + cur_chunk * p.v_sc + cur_tin * p.v_sl);
+        }
+    };
+    // the (full) tile at the cursor lies inside one chunk
+    auto in_chunk = [&](bool full) {
+        return ROWPASS && full && off32 && cur_tin + KVB <= LC;
+    };
+    // `full`: every token of the tile is below Lkv (all tiles but the tail).
+    // In a DMA instantiation the in-chunk tiles go through stage_dma instead.
     auto stage_load = [&](int t0, bool full) {
-        if (ROWPASS && full && off32 && cur_tin + KVB <= LC) {
+        if (!DMA && in_chunk(full)) {
             // The tile lies inside one chunk: uniform cursor + fixed lane
             // offset, and registers about to be overwritten are not zeroed.
             const auto krs = tile_rsrc(kcur);
@@ -304,7 +381,6 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
 #pragma unroll
             for (int i = 0; i < NLD; ++i) {
                 const int t_local = stage_row(i);
-                const int d8 = stage_col(i);
                 int tin = cur_tin + t_local;
                 int ch = cur_chunk;
                 while (tin >= LC) {
@@ -315,34 +391,75 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
                 vreg[i] = uint4{0, 0, 0, 0};
                 if (stage_d_ok(i) && t0 + t_local < Lkv) {
                     kreg[i] = *reinterpret_cast<const uint4*>(
-                        kbase + ch * p.k_sc + tin * p.k_sl + d8 * 8);
+                        kbase + ch * p.k_sc + tin * p.k_sl + stage_kcol(i) * 8);
                     vreg[i] = *reinterpret_cast<const uint4*>(
-                        vbase + ch * p.v_sc + tin * p.v_sl + d8 * 8);
+                        vbase + ch * p.v_sc + tin * p.v_sl + stage_vcol(i) * 8);
                 }
             }
         }
-        cur_tin += KVB;
-        kcur += KVB * p.k_sl * 2;
-        vcur += KVB * p.v_sl * 2;
-        if (cur_tin >= LC) {  // chunk crossing: re-seat the cursor
-            do {
-                cur_tin -= LC;
-                ++cur_chunk;
-            } while (cur_tin >= LC);
-            kcur = reinterpret_cast<const char*>(kbase + cur_chunk * p.k_sc + cur_tin * p.k_sl);
-            vcur = reinterpret_cast<const char*>(vbase + cur_chunk * p.v_sc + cur_tin * p.v_sl);
-        }
+        advance_cursor();
     };
-    auto stage_write = [&]() {
+    // LDS-DMA of the in-chunk tile at the cursor into buffer wbuf: per wave
+    // and pass one 1 KiB piece of K and one of V, no register in between. The
+    // wave's piece of pass i is rows i*64 + wave*8 .. +7, the linear slots of
+    // its lanes; the descriptor, the lane offset and the pass step are those
+    // of the register path.
+    //
+    // The four loads are one asm statement: through the builtin the compiler
+    // counts an LDS-DMA as a store to LDS that any later ds_read may alias and
+    // puts vmcnt(3..0) in front of the first QK^T reads of the tile being
+    // computed, which drains the prefetch on the spot. Unseen by its counting
+    // they stay in flight across the compute; the vmcnt(0) before the next
+    // barrier retires them, and its own vmcnt waits can only come out stricter
+    // than needed (loads return in order). M0, the LDS destination of the
+    // wave-instruction, is the compiler's: saved and put back.
+    auto stage_dma = [&](int wbuf) {
+        static_assert(!DMA || NLD == 2);
+        auto words = [](const char* cur) {
+            const uint64_t a = reinterpret_cast<uint64_t>(cur);
+            return u32x4{(uint32_t)a, (uint32_t)(a >> 32) & 0xFFFFu, 0xFFFFFFFFu, 0x00020000u};
+        };
+        const u32x4 krs = words(kcur);
+        const u32x4 vrs = words(vcur);
+        const uint32_t piece = __builtin_amdgcn_readfirstlane(wave) * (WAVE_SIZE * 16);
+        const uint32_t kd0 = lds_addr(&k_lds[wbuf * K_BYTES]) + piece;
+        const uint32_t vd0 = lds_addr(&v_lds[wbuf * V_BYTES]) + piece;
+        const uint32_t kd1 = kd0 + NT * 16, vd1 = vd0 + NT * 16;
+        uint32_t keep;
+        asm volatile(
+            "s_mov_b32 %0, m0\n\t"
+            "s_mov_b32 m0, %5\n\ts_nop 0\n\t"
+            "buffer_load_dwordx4 %1, %3, 0 offen lds\n\t"
+            "s_mov_b32 m0, %6\n\ts_nop 0\n\t"
+            "buffer_load_dwordx4 %2, %4, 0 offen lds\n\t"
+            "s_mov_b32 m0, %7\n\ts_nop 0\n\t"
+            "buffer_load_dwordx4 %1, %3, %9 offen lds\n\t"
+            "s_mov_b32 m0, %8\n\ts_nop 0\n\t"
+            "buffer_load_dwordx4 %2, %4, %10 offen lds\n\t"
+            "s_mov_b32 m0, %0"
+            : "=&s"(keep)
+            : "v"(koff), "v"(voff), "s"(krs), "s"(vrs), "s"(kd0), "s"(vd0), "s"(kd1), "s"(vd1),
+              "s"(k_pass), "s"(v_pass)
+            : "memory");
+        advance_cursor();
+    };
+    // wbuf: the buffer written (DMA instantiations; the others have one)
+    auto stage_write = [&](int wbuf) {
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
-            const int t_local = stage_row(i);
-            const int d8 = stage_col(i);
-            char* kdst = &k_lds[t_local * K_ROW + d8 * 16];
-            *reinterpret_cast<uint2*>(kdst) = uint2{kreg[i].x, kreg[i].y};
-            *reinterpret_cast<uint2*>(kdst + 8) = uint2{kreg[i].z, kreg[i].w};
-            *reinterpret_cast<uint4*>(
-                &v_lds[t_local * V_ROW + ((d8 * 16) ^ v_swz<DPAD>(t_local))]) = vreg[i];
+            if constexpr (DMA) {
+                const int slot = (tid + i * NT) * 16;
+                *reinterpret_cast<uint4*>(&k_lds[wbuf * K_BYTES + slot]) = kreg[i];
+                *reinterpret_cast<uint4*>(&v_lds[wbuf * V_BYTES + slot]) = vreg[i];
+            } else {
+                const int t_local = stage_row(i);
+                const int d8 = stage_col(i);
+                char* kdst = &k_lds[t_local * K_ROW + d8 * 16];
+                *reinterpret_cast<uint2*>(kdst) = uint2{kreg[i].x, kreg[i].y};
+                *reinterpret_cast<uint2*>(kdst + 8) = uint2{kreg[i].z, kreg[i].w};
+                *reinterpret_cast<uint4*>(
+                    &v_lds[t_local * V_ROW + ((d8 * 16) ^ v_swz<DPAD>(t_local))]) = vreg[i];
+            }
         }
     };
 
@@ -371,14 +488,20 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
         __builtin_amdgcn_s_setprio(1);  // favor the MFMA wave (guide T5)
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-            const int t = st * 32 + lo;
-            // lds_frag_b64x2 spelled out: through the helper the DPAD-64 plain
-            // kernels schedule their staging writes differently
-            const char* ksrc = &k_lds[t * K_ROW + (ks * 16 + hi * 8) * 2];
-            const uint2 k0 = *reinterpret_cast<const uint2*>(ksrc);
-            const uint2 k1 = *reinterpret_cast<const uint2*>(ksrc + 8);
-            const uint4 kk{k0.x, k0.y, k1.x, k1.y};
-            const short8 kfrag = __builtin_bit_cast(short8, kk);
+            short8 kfrag;
+            if constexpr (DMA) {
+                // one b128 read from the swizzled 128 B rows
+                kfrag = *reinterpret_cast<const short8*>(&k_lds[krd[ks] + st * 32 * K_ROW]);
+            } else {
+                const int t = st * 32 + lo;
+                // lds_frag_b64x2 spelled out: through the helper the DPAD-64
+                // plain kernels schedule their staging writes differently
+                const char* ksrc = &k_lds[t * K_ROW + (ks * 16 + hi * 8) * 2];
+                const uint2 k0 = *reinterpret_cast<const uint2*>(ksrc);
+                const uint2 k1 = *reinterpret_cast<const uint2*>(ksrc + 8);
+                const uint4 kk{k0.x, k0.y, k1.x, k1.y};
+                kfrag = __builtin_bit_cast(short8, kk);
+            }
             s = mfma_32x32x16<F16>(kfrag, qf[ks], s);
         }
         __builtin_amdgcn_s_setprio(0);
@@ -475,27 +598,77 @@ __attribute__((amdgpu_waves_per_eu(DPAD == 64 ? 4 : 2))) void flash_attn_kernel(
     const int tile0 = LSE ? tile_lo : 0;
     const int n_full = LSE ? min(tile_hi, Lkv / KVB) : Lkv / KVB;
     const int rem = LSE && tile_hi * KVB <= Lkv ? 0 : Lkv % KVB;
-    if (Lkv > 0) {
-        stage_load(tile0 * KVB, tile0 < n_full);
-        stage_write();
-        lds_barrier();
-    }
-    // Q has landed: without this the compiler cannot count the conditional
-    // loads behind the Q loads and drains the prefetch at the first QK^T
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only
-    for (int tile = tile0; tile < n_full; ++tile) {
-        const int t0 = tile * KVB;
-        const bool next_full = tile + 1 < n_full;
-        // split staging: the next tile's loads are in flight across the compute
-        auto load_next = [&]() {
-            if (next_full || rem) stage_load(t0 + KVB, next_full);
+    if constexpr (DMA) {
+        // Two buffers, one barrier per tile. Tile t is read from buffer rb
+        // while tile t+1 goes into the other one: by LDS-DMA, issued right
+        // behind the barrier, if it lies inside one chunk, else through
+        // registers after the compute (load, then ds_write: that keeps the 16
+        // staging registers out of the compute's live range; such tiles are
+        // one in 28 at LC = 3600, none without chunks). The
+        // barrier at the top of the next iteration, with this wave's DMA
+        // (vmcnt) and LDS writes (lgkmcnt) retired in front of it, publishes
+        // either kind and tells that every wave is done reading the buffer the
+        // tile after that will land in; so the two kinds alternate freely.
+        auto publish = [] {
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         };
-        load_next();
-        compute.template operator()<KVB / 32, false>(t0);
-        if (next_full || rem) {
-            lds_barrier();  // every wave is done reading this tile
-            stage_write();
+        int rb = 0;
+        auto flip = [&]() {
+            rb ^= 1;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) krd[ks] ^= K_BYTES;
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) vrd[dt] ^= V_BYTES;
+        };
+        if (Lkv > 0) {
+            if (in_chunk(tile0 < n_full)) {
+                stage_dma(0);
+            } else {
+                stage_load(tile0 * KVB, tile0 < n_full);
+                stage_write(0);
+            }
+        }
+        // Q has landed: else the compiler carries the pending Q loads into the
+        // loop and waits for them, and with them the DMA, at every first QK^T
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only
+        for (int tile = tile0; tile < n_full; ++tile) {
+            const int t0 = tile * KVB;
+            const bool next_full = tile + 1 < n_full;
+            publish();
+            const bool more = next_full || rem;
+            const bool by_dma = more && in_chunk(next_full);
+            if (by_dma) stage_dma(rb ^ 1);
+            compute.template operator()<KVB / 32, false>(t0);
+            if (more && !by_dma) {
+                stage_load(t0 + KVB, next_full);
+                stage_write(rb ^ 1);
+            }
+            flip();
+        }
+        if (rem) publish();
+    } else {
+        if (Lkv > 0) {
+            stage_load(tile0 * KVB, tile0 < n_full);
+            stage_write(0);
             lds_barrier();
+        }
+        // Q has landed: without this the compiler cannot count the conditional
+        // loads behind the Q loads and drains the prefetch at the first QK^T
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) only
+        for (int tile = tile0; tile < n_full; ++tile) {
+            const int t0 = tile * KVB;
+            const bool next_full = tile + 1 < n_full;
+            // split staging: the next tile's loads are in flight across the compute
+            auto load_next = [&]() {
+                if (next_full || rem) stage_load(t0 + KVB, next_full);
+            };
+            load_next();
+            compute.template operator()<KVB / 32, false>(t0);
+            if (next_full || rem) {
+                lds_barrier();  // every wave is done reading this tile
+                stage_write(0);
+                lds_barrier();
+            }
         }
     }
     if (rem == 64)
