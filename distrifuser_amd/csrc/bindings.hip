@@ -8,6 +8,7 @@
 
 #include <array>
 
+#include "boundary_plan.h"
 #include "kernels.h"
 
 namespace {
@@ -53,6 +54,25 @@ const void* gn_affine(const c10::optional<at::Tensor>& t, const at::Tensor& x, a
     return keep.data_ptr();
 }
 
+// The apply pass of both GroupNorm entries: NCHW like x, or [N, HW, C] (tokens)
+at::Tensor gn_apply_out(const at::Tensor& x, const float* mean, const float* meansq,
+                        const void* wp, const void* bp, double eps, int g, bool silu,
+                        bool tokens) {
+    const int64_t n = x.size(0), c = x.size(1), hw = x.size(2) * x.size(3);
+    if (!tokens) {
+        auto y = at::empty_like(x);
+        launch_gn_apply(x.data_ptr(), y.data_ptr(), mean, meansq, wp, bp, (float)eps, hw, (int)c,
+                        g, (int)n, silu, dtype_of(x), cur_stream());
+        return y;
+    }
+    auto y = at::empty({n, hw, c}, x.options());
+    const BoundaryPlan pl = boundary_plan(n, c, hw, (int)x.element_size(), true);
+    TORCH_CHECK(pl.ok || pl.empty, "group_norm tokens: shape too large for one launch");
+    launch_gn_apply_tokens(x.data_ptr(), y.data_ptr(), mean, meansq, wp, bp, (float)eps, hw,
+                           (int)c, g, (int)n, silu, dtype_of(x), cur_stream());
+    return y;
+}
+
 at::Tensor group_norm_stats(const at::Tensor& x_, int64_t num_groups) {
     TORCH_CHECK(x_.is_cuda() && x_.dim() == 4, "x must be CUDA [N,C,H,W]");
     auto x = x_.contiguous();
@@ -69,10 +89,11 @@ at::Tensor group_norm_stats(const at::Tensor& x_, int64_t num_groups) {
 
 at::Tensor group_norm_apply(const at::Tensor& x_, const at::Tensor& mean_,
                             const at::Tensor& meansq_, const c10::optional<at::Tensor>& w_,
-                            const c10::optional<at::Tensor>& b_, double eps, bool silu) {
+                            const c10::optional<at::Tensor>& b_, double eps, bool silu,
+                            bool tokens) {
     TORCH_CHECK(x_.is_cuda() && x_.dim() == 4);
     auto x = x_.contiguous();
-    const int64_t n = x.size(0), c = x.size(1), hw = x.size(2) * x.size(3);
+    const int64_t n = x.size(0), c = x.size(1);
     auto mean = mean_.to(at::kFloat).contiguous().view({-1});
     auto meansq = meansq_.to(at::kFloat).contiguous().view({-1});
     TORCH_CHECK(mean.numel() % n == 0);
@@ -81,15 +102,14 @@ at::Tensor group_norm_apply(const at::Tensor& x_, const at::Tensor& mean_,
     at::Tensor w, b;
     const void* wp = gn_affine(w_, x, w);
     const void* bp = gn_affine(b_, x, b);
-    auto y = at::empty_like(x);
-    launch_gn_apply(x.data_ptr(), y.data_ptr(), mean.data_ptr<float>(), meansq.data_ptr<float>(),
-                    wp, bp, (float)eps, hw, (int)c, g, (int)n, silu, dtype_of(x), cur_stream());
-    return y;
+    return gn_apply_out(x, mean.data_ptr<float>(), meansq.data_ptr<float>(), wp, bp, eps, g, silu,
+                        tokens);
 }
 
 at::Tensor group_norm_silu(const at::Tensor& x_, int64_t num_groups,
                            const c10::optional<at::Tensor>& w_,
-                           const c10::optional<at::Tensor>& b_, double eps, bool silu) {
+                           const c10::optional<at::Tensor>& b_, double eps, bool silu,
+                           bool tokens) {
     TORCH_CHECK(x_.is_cuda() && x_.dim() == 4);
     auto x = x_.contiguous();
     const int64_t n = x.size(0), c = x.size(1), hw = x.size(2) * x.size(3);
@@ -104,11 +124,34 @@ at::Tensor group_norm_silu(const at::Tensor& x_, int64_t num_groups,
     at::Tensor w, b;
     const void* wp = gn_affine(w_, x, w);
     const void* bp = gn_affine(b_, x, b);
-    auto y = at::empty_like(x);
-    launch_gn_apply(x.data_ptr(), y.data_ptr(), moments.data_ptr<float>(),
-                    moments.data_ptr<float>() + ngt, wp, bp, (float)eps, hw, (int)c,
-                    (int)num_groups, (int)n, silu, dtype_of(x), cur_stream());
-    return y;
+    return gn_apply_out(x, moments.data_ptr<float>(), moments.data_ptr<float>() + ngt, wp, bp, eps,
+                        (int)num_groups, silu, tokens);
+}
+
+// y [N, HW, C] + residual [N, C, H, W] -> [N, C, H, W] contiguous. residual may
+// have any batch and channel stride; its (H, W) plane must be contiguous.
+at::Tensor tokens_add_nchw(const at::Tensor& y_, const at::Tensor& residual) {
+    TORCH_CHECK(y_.is_cuda() && y_.dim() == 3 && residual.is_cuda() && residual.dim() == 4,
+                "tokens_add_nchw: y [N,HW,C] and residual [N,C,H,W] on the GPU");
+    TORCH_CHECK(y_.scalar_type() == residual.scalar_type(),
+                "tokens_add_nchw: residual must have y's dtype (", y_.scalar_type(), "), got ",
+                residual.scalar_type());
+    const int64_t n = residual.size(0), c = residual.size(1);
+    const int64_t hw = residual.size(2) * residual.size(3);
+    TORCH_CHECK(y_.size(0) == n && y_.size(1) == hw && y_.size(2) == c,
+                "tokens_add_nchw: y must be [N, H*W, C] of residual [N, C, H, W]");
+    const int64_t sizes[4] = {n, c, residual.size(2), residual.size(3)};
+    const int64_t strides[4] = {residual.stride(0), residual.stride(1), residual.stride(2),
+                                residual.stride(3)};
+    TORCH_CHECK(boundary_plane_contiguous(sizes, strides),
+                "tokens_add_nchw: residual's (H, W) plane must be contiguous");
+    auto y = y_.contiguous();
+    auto out = at::empty({n, c, residual.size(2), residual.size(3)}, y.options());
+    const BoundaryPlan pl = boundary_plan(n, c, hw, (int)y.element_size(), true);
+    TORCH_CHECK(pl.ok || pl.empty, "tokens_add_nchw: shape too large for one launch");
+    launch_tokens_add_nchw(y.data_ptr(), residual.data_ptr(), out.data_ptr(), hw, (int)c, (int)n,
+                           strides[0], strides[1], dtype_of(y), cur_stream());
+    return out;
 }
 
 at::Tensor gn_merge_stats(const at::Tensor& buffer, int64_t slot_off, int64_t own,
@@ -531,8 +574,17 @@ std::vector<at::Tensor> mfma_probe32(const at::Tensor& a, const at::Tensor& b) {
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("group_norm_stats", &group_norm_stats, "per-group moments [2,N,G,1,1,1]");
-    m.def("group_norm_apply", &group_norm_apply, "normalize+affine(+SiLU) from given moments");
-    m.def("group_norm_silu", &group_norm_silu, "fused GroupNorm(+SiLU)");
+    m.def("group_norm_apply", &group_norm_apply,
+          "normalize+affine(+SiLU) from given moments; tokens: write [N, HW, C]",
+          pybind11::arg("x"), pybind11::arg("mean"), pybind11::arg("meansq"),
+          pybind11::arg("weight"), pybind11::arg("bias"), pybind11::arg("eps"),
+          pybind11::arg("silu"), pybind11::arg("tokens") = false);
+    m.def("group_norm_silu", &group_norm_silu, "fused GroupNorm(+SiLU); tokens: write [N, HW, C]",
+          pybind11::arg("x"), pybind11::arg("num_groups"), pybind11::arg("weight"),
+          pybind11::arg("bias"), pybind11::arg("eps"), pybind11::arg("silu"),
+          pybind11::arg("tokens") = false);
+    m.def("tokens_add_nchw", &tokens_add_nchw,
+          "y [N, HW, C] + residual [N, C, H, W] -> [N, C, H, W] (transposing residual add)");
     m.def("geglu", &geglu, "a * gelu(gate) over last-dim halves");
     m.def("gn_merge_stats", &gn_merge_stats,
           "merge stale peer GN moments with fresh local ones (one launch)");

@@ -8,6 +8,7 @@
 // one atomicAdd pair per block (device-scope atomics are XCD-safe, guide §6
 // G12); each (sample, group) slab is contiguous in NCHW.
 
+#include "boundary_plan.h"
 #include "common.h"
 #include "kernels.h"
 #include <algorithm>
@@ -150,6 +151,296 @@ void gn_apply_t(const void* x, void* y, const float* mean, const float* meansq, 
     }
 }
 
+// ---- NCHW <-> token-major transposing kernels --------------------------------
+// The transformer boundary: GroupNorm apply that writes [N, HW, C] (the layout
+// proj_in reads) and the closing residual add that reads [N, HW, C] and writes
+// NCHW. Both are tiled transposes through LDS; launch arithmetic is in
+// boundary_plan.h.
+//
+// Vector path (16-bit types, HW % 8 == 0, C % 8 == 0): a block owns 64
+// channels x 64 pixels. The LDS image is pixel-major, [64 pixels][64 channels]
+// = 32 dwords per pixel row, each dword a pair of neighbouring channels. The
+// 16-byte chunk q (8 channels) of pixel row p sits at chunk q ^ ((p >> 3) & 7):
+//  - NCHW side, thread (cp = t >> 3, pv = t & 7) holds channels 2cp, 2cp+1 at
+//    pixels 8pv..8pv+7 and moves 8 dwords, dword j at row 8pv + j. The 32
+//    lanes of a b32 lane group have 4 consecutive cp of one chunk and all 8
+//    pv, so ((q ^ pv) << 2 | cp & 3) covers the 32 banks once.
+//  - token side, thread (p = t >> 3, q = t & 7) moves one 16-byte chunk; the 8
+//    lanes of a pixel row cover its 32 dwords once.
+constexpr int BT = BOUNDARY_VEC_TILE;
+
+__device__ __forceinline__ int bt_dword(int prow, int cp) {
+    return prow * (BT / 2) + (((cp >> 2) ^ ((prow >> 3) & 7)) << 2 | (cp & 3));
+}
+__device__ __forceinline__ int bt_chunk(int prow, int q) {
+    return prow * (BT / 2) + ((q ^ ((prow >> 3) & 7)) << 2);
+}
+
+template <typename T>
+__device__ __forceinline__ uint32_t bits16(T v) {
+    return (uint32_t)__builtin_bit_cast(uint16_t, v);
+}
+
+// The per-channel scale / shift and the per-element value of gn_apply_kernel,
+// with its floating-point contraction written out. The compiler fuses
+// gn_apply_kernel's `m * sc` and `x * sc` into fmas in its vector variants and
+// keeps them as a multiply and an add / subtract in its scalar variants (there
+// it pairs the two multiplies into one packed instruction). FUSED says which
+// of the two the NCHW kernel takes for the same tensor (HW % VecN == 0), so a
+// token-layout result is bit-identical to the NCHW one whichever tile path
+// produces it (tests/test_transformer_boundary_gpu.py holds both to that).
+template <bool FUSED>
+__device__ __forceinline__ void gn_scale_shift(float m, float msq, float eps, float wv, float bv,
+                                               float& sc, float& sh) {
+#pragma clang fp contract(off)  // every fma below is spelled out
+    float var = __builtin_fmaf(-m, m, msq);
+    var = var < 0.f ? 0.f : var;
+    const float inv = rsqrtf(var + eps);
+    sc = wv * inv;
+    if (FUSED) {
+        sh = __builtin_fmaf(-m, sc, bv);
+    } else {
+        const float ms = m * sc;
+        sh = bv - ms;
+    }
+}
+template <bool FUSED>
+__device__ __forceinline__ float gn_norm(float x, float sc, float sh) {
+#pragma clang fp contract(off)
+    if (FUSED) return __builtin_fmaf(x, sc, sh);
+    const float xs = x * sc;
+    return xs + sh;
+}
+
+template <typename T, bool SILU>
+__global__ __launch_bounds__(BOUNDARY_THREADS) void gn_apply_tokens_vec_kernel(
+    const T* __restrict__ x, T* __restrict__ y, const float* __restrict__ mean,
+    const float* __restrict__ meansq, const T* __restrict__ w, const T* __restrict__ b, float eps,
+    int64_t hw, int C, int G) {
+    static_assert(sizeof(T) == 2, "16-bit types only");
+    __shared__ __attribute__((aligned(16))) uint32_t tile[BT * BT / 2];
+    const int t = threadIdx.x;
+    const int64_t n = blockIdx.z;
+    const int c0 = blockIdx.y * BT;
+    const int64_t p0 = (int64_t)blockIdx.x * BT;
+    const int gs = C / G;
+    {
+        const int pv = t & 7, cp = t >> 3;
+        const int c = c0 + 2 * cp;
+        const int64_t p = p0 + pv * 8;
+        uint32_t packed[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (c < C && p < hw) {  // C is even: channel c + 1 exists with c
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int ch = c + h;
+                const int g = ch / gs;
+                float sc, sh;  // HW % 8 == 0 here: the NCHW kernel's vector variant
+                gn_scale_shift<true>(mean[n * G + g], meansq[n * G + g], eps,
+                                     w ? to_f32(w[ch]) : 1.f, b ? to_f32(b[ch]) : 0.f, sc, sh);
+                const uint4 raw = *reinterpret_cast<const uint4*>(x + (n * C + ch) * hw + p);
+                const T* e = reinterpret_cast<const T*>(&raw);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    float f = gn_norm<true>(to_f32(e[j]), sc, sh);
+                    if (SILU) f = siluf(f);
+                    packed[j] |= bits16(from_f32<T>(f)) << (16 * h);
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) tile[bt_dword(pv * 8 + j, cp)] = packed[j];
+    }
+    __syncthreads();
+    {
+        const int q = t & 7;
+        const int ch = c0 + q * 8;
+#pragma unroll
+        for (int pass = 0; pass < 2; ++pass) {
+            const int pr = (t >> 3) + 32 * pass;
+            const int64_t pix = p0 + pr;
+            const uint4 v = *reinterpret_cast<const uint4*>(&tile[bt_chunk(pr, q)]);
+            if (pix < hw && ch < C) *reinterpret_cast<uint4*>(y + (n * hw + pix) * C + ch) = v;
+        }
+    }
+}
+
+// Any type, any HW, any C % G == 0: 32 x 32 elements per block through a padded
+// fp32 tile (the value is rounded once, at the store, as in gn_apply_kernel).
+template <typename T, bool SILU, bool FUSED>
+__global__ __launch_bounds__(BOUNDARY_THREADS) void gn_apply_tokens_scalar_kernel(
+    const T* __restrict__ x, T* __restrict__ y, const float* __restrict__ mean,
+    const float* __restrict__ meansq, const T* __restrict__ w, const T* __restrict__ b, float eps,
+    int64_t hw, int C, int G) {
+    constexpr int S = BOUNDARY_SCALAR_TILE;
+    __shared__ float tile[S][S + 1];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int64_t n = blockIdx.z;
+    const int c0 = blockIdx.y * S;
+    const int64_t p0 = (int64_t)blockIdx.x * S;
+    const int gs = C / G;
+#pragma unroll
+    for (int i = 0; i < S / 8; ++i) {
+        const int cl = ty + 8 * i;
+        const int c = c0 + cl;
+        const int64_t p = p0 + tx;
+        if (c < C && p < hw) {
+            const int g = c / gs;
+            float sc, sh;
+            gn_scale_shift<FUSED>(mean[n * G + g], meansq[n * G + g], eps,
+                                  w ? to_f32(w[c]) : 1.f, b ? to_f32(b[c]) : 0.f, sc, sh);
+            float f = gn_norm<FUSED>(to_f32(x[(n * C + c) * hw + p]), sc, sh);
+            if (SILU) f = siluf(f);
+            tile[cl][tx] = f;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < S / 8; ++i) {
+        const int pl = ty + 8 * i;
+        const int64_t p = p0 + pl;
+        const int c = c0 + tx;
+        if (c < C && p < hw) y[(n * hw + p) * C + c] = from_f32<T>(tile[tx][pl]);
+    }
+}
+
+// out[n, c, p] = round(float(y[n, p, c]) + float(res[n, c, p])): the mirror of
+// gn_apply_tokens_vec_kernel. res has batch / channel strides rs_n / rs_c
+// (elements) and a contiguous pixel plane; out is contiguous NCHW.
+template <typename T>
+__global__ __launch_bounds__(BOUNDARY_THREADS) void tokens_add_nchw_vec_kernel(
+    const T* __restrict__ y, const T* __restrict__ res, T* __restrict__ out, int64_t hw, int C,
+    int64_t rs_n, int64_t rs_c) {
+    static_assert(sizeof(T) == 2, "16-bit types only");
+    __shared__ __attribute__((aligned(16))) uint32_t tile[BT * BT / 2];
+    const int t = threadIdx.x;
+    const int64_t n = blockIdx.z;
+    const int c0 = blockIdx.y * BT;
+    const int64_t p0 = (int64_t)blockIdx.x * BT;
+    // NCHW-side coordinates; the residual loads go out before the transpose
+    const int pv = t & 7, cp = t >> 3;
+    const int c = c0 + 2 * cp;
+    const int64_t p = p0 + pv * 8;
+    const bool live = c < C && p < hw;
+    uint4 r[2] = {uint4{0, 0, 0, 0}, uint4{0, 0, 0, 0}};
+    if (live) {
+        r[0] = *reinterpret_cast<const uint4*>(res + n * rs_n + (int64_t)c * rs_c + p);
+        r[1] = *reinterpret_cast<const uint4*>(res + n * rs_n + (int64_t)(c + 1) * rs_c + p);
+    }
+    {
+        const int q = t & 7;
+        const int ch = c0 + q * 8;
+#pragma unroll
+        for (int pass = 0; pass < 2; ++pass) {
+            const int pr = (t >> 3) + 32 * pass;
+            const int64_t pix = p0 + pr;
+            uint4 v{0, 0, 0, 0};
+            if (pix < hw && ch < C) v = *reinterpret_cast<const uint4*>(y + (n * hw + pix) * C + ch);
+            *reinterpret_cast<uint4*>(&tile[bt_chunk(pr, q)]) = v;
+        }
+    }
+    __syncthreads();
+    if (live) {
+        uint32_t d[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) d[j] = tile[bt_dword(pv * 8 + j, cp)];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const T* re = reinterpret_cast<const T*>(&r[h]);
+            uint4 outv;
+            T* o = reinterpret_cast<T*>(&outv);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const T yv = __builtin_bit_cast(T, (uint16_t)(d[j] >> (16 * h)));
+                o[j] = from_f32<T>(to_f32(yv) + to_f32(re[j]));
+            }
+            *reinterpret_cast<uint4*>(out + (n * C + c + h) * hw + p) = outv;
+        }
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(BOUNDARY_THREADS) void tokens_add_nchw_scalar_kernel(
+    const T* __restrict__ y, const T* __restrict__ res, T* __restrict__ out, int64_t hw, int C,
+    int64_t rs_n, int64_t rs_c) {
+    constexpr int S = BOUNDARY_SCALAR_TILE;
+    __shared__ float tile[S][S + 1];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int64_t n = blockIdx.z;
+    const int c0 = blockIdx.y * S;
+    const int64_t p0 = (int64_t)blockIdx.x * S;
+#pragma unroll
+    for (int i = 0; i < S / 8; ++i) {
+        const int pl = ty + 8 * i;
+        const int64_t p = p0 + pl;
+        const int c = c0 + tx;
+        if (c < C && p < hw) tile[pl][tx] = to_f32(y[(n * hw + p) * C + c]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < S / 8; ++i) {
+        const int cl = ty + 8 * i;
+        const int c = c0 + cl;
+        const int64_t p = p0 + tx;
+        if (c < C && p < hw)
+            out[(n * C + c) * hw + p] =
+                from_f32<T>(tile[tx][cl] + to_f32(res[n * rs_n + (int64_t)c * rs_c + p]));
+    }
+}
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+template <typename T>
+void gn_apply_tokens_t(const void* x, void* y, const float* mean, const float* meansq,
+                       const void* w, const void* b, float eps, int64_t hw, int C, int G, int N,
+                       bool silu, hipStream_t stream) {
+    const BoundaryPlan pl =
+        boundary_plan(N, C, hw, (int)sizeof(T), aligned16(x) && aligned16(y));
+    if (!pl.ok) return;  // empty; the binding rejects an oversized grid
+    const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y, (unsigned)pl.grid_z);
+#define DFA_GN_TOKENS_LAUNCH(...)                                                            \
+    __VA_ARGS__<<<grid, BOUNDARY_THREADS, 0, stream>>>((const T*)x, (T*)y, mean, meansq,     \
+                                                       (const T*)w, (const T*)b, eps, hw, C, G)
+    if constexpr (sizeof(T) == 2) {
+        if (pl.vec) {
+            if (silu)
+                DFA_GN_TOKENS_LAUNCH(gn_apply_tokens_vec_kernel<T, true>);
+            else
+                DFA_GN_TOKENS_LAUNCH(gn_apply_tokens_vec_kernel<T, false>);
+            return;
+        }
+    }
+    // the arithmetic form of the NCHW kernel for this tensor (gn_apply_t's choice)
+    const bool fused = (hw % VecN<T>::value) == 0;
+    if (silu && fused)
+        DFA_GN_TOKENS_LAUNCH(gn_apply_tokens_scalar_kernel<T, true, true>);
+    else if (silu)
+        DFA_GN_TOKENS_LAUNCH(gn_apply_tokens_scalar_kernel<T, true, false>);
+    else if (fused)
+        DFA_GN_TOKENS_LAUNCH(gn_apply_tokens_scalar_kernel<T, false, true>);
+    else
+        DFA_GN_TOKENS_LAUNCH(gn_apply_tokens_scalar_kernel<T, false, false>);
+#undef DFA_GN_TOKENS_LAUNCH
+}
+
+template <typename T>
+void tokens_add_nchw_t(const void* y, const void* res, void* out, int64_t hw, int C, int N,
+                       int64_t rs_n, int64_t rs_c, hipStream_t stream) {
+    const bool al = aligned16(y) && aligned16(res) && aligned16(out) && rs_n % 8 == 0 &&
+                    rs_c % 8 == 0;
+    const BoundaryPlan pl = boundary_plan(N, C, hw, (int)sizeof(T), al);
+    if (!pl.ok) return;
+    const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y, (unsigned)pl.grid_z);
+    if constexpr (sizeof(T) == 2) {
+        if (pl.vec) {
+            tokens_add_nchw_vec_kernel<T><<<grid, BOUNDARY_THREADS, 0, stream>>>(
+                (const T*)y, (const T*)res, (T*)out, hw, C, rs_n, rs_c);
+            return;
+        }
+    }
+    tokens_add_nchw_scalar_kernel<T><<<grid, BOUNDARY_THREADS, 0, stream>>>(
+        (const T*)y, (const T*)res, (T*)out, hw, C, rs_n, rs_c);
+}
+
 template <typename T, bool CORRECTED>
 __global__ void gn_merge_stats_kernel(T* __restrict__ buffer, int64_t row_stride,
                                       int64_t slot_off, int n_peers, int own,
@@ -275,6 +566,44 @@ void launch_gn_apply(const void* x, void* y, const float* mean, const float* mea
             break;
         default:
             gn_apply_t<float>(x, y, mean, meansq, weight, bias, eps, hw, C, G, N, silu, stream);
+            break;
+    }
+}
+
+void launch_gn_apply_tokens(const void* x, void* y, const float* mean, const float* meansq,
+                            const void* weight, const void* bias, float eps, int64_t hw, int C,
+                            int G, int N, bool silu, int dtype, hipStream_t stream) {
+    switch (dtype) {
+        case DFA_BF16:
+            gn_apply_tokens_t<bf16_t>(x, y, mean, meansq, weight, bias, eps, hw, C, G, N, silu,
+                                      stream);
+            break;
+        case DFA_F16:
+            gn_apply_tokens_t<f16_t>(x, y, mean, meansq, weight, bias, eps, hw, C, G, N, silu,
+                                     stream);
+            break;
+        default:
+            gn_apply_tokens_t<float>(x, y, mean, meansq, weight, bias, eps, hw, C, G, N, silu,
+                                     stream);
+            break;
+    }
+}
+
+void launch_tokens_add_nchw(const void* y, const void* residual, void* out, int64_t hw, int C,
+                            int N, int64_t res_stride_n, int64_t res_stride_c, int dtype,
+                            hipStream_t stream) {
+    switch (dtype) {
+        case DFA_BF16:
+            tokens_add_nchw_t<bf16_t>(y, residual, out, hw, C, N, res_stride_n, res_stride_c,
+                                      stream);
+            break;
+        case DFA_F16:
+            tokens_add_nchw_t<f16_t>(y, residual, out, hw, C, N, res_stride_n, res_stride_c,
+                                     stream);
+            break;
+        default:
+            tokens_add_nchw_t<float>(y, residual, out, hw, C, N, res_stride_n, res_stride_c,
+                                     stream);
             break;
     }
 }

@@ -18,6 +18,24 @@ void launch_gn_apply(const void* x, void* y, const float* mean, const float* mea
                      const void* weight, const void* bias, float eps, int64_t hw,
                      int C, int G, int N, bool silu, int dtype, hipStream_t stream);
 
+// launch_gn_apply with a token-major result: x [N, C, HW] contiguous in,
+// y [N, HW, C] contiguous out; the same value per element (a tiled transpose
+// through LDS). 16-byte accesses for 16-bit types when HW % 8 == 0, C % 8 == 0
+// and both pointers are 16-byte aligned, else an element-wise tile; any dtype.
+// The caller keeps C tiles and N within 65535 (boundary_plan.h).
+void launch_gn_apply_tokens(const void* x, void* y, const float* mean, const float* meansq,
+                            const void* weight, const void* bias, float eps, int64_t hw,
+                            int C, int G, int N, bool silu, int dtype, hipStream_t stream);
+
+// ---- token -> NCHW transposing residual add ---------------------------------
+// out[n, c, p] = round(float(y[n, p, c]) + float(residual[n, c, p])); y [N, HW, C]
+// and out [N, C, HW] contiguous, residual with batch / channel strides in
+// elements and a contiguous pixel plane. Same vector / scalar split as above
+// (the vector path also needs both residual strides to be multiples of 8).
+void launch_tokens_add_nchw(const void* y, const void* residual, void* out, int64_t hw, int C,
+                            int N, int64_t res_stride_n, int64_t res_stride_c, int dtype,
+                            hipStream_t stream);
+
 // ---- displaced-GN stat merge ------------------------------------------------
 // Merge per-peer stale GroupNorm moments with this rank's fresh ones in ONE
 // launch (replaces a ~10-kernel torch composition per GN layer):

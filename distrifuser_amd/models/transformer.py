@@ -2,6 +2,8 @@
 
 from __future__ import annotations
 
+import os
+
 import torch
 from torch import nn
 
@@ -70,6 +72,12 @@ class Transformer2DModel(nn.Module):
         super().__init__()
         inner = heads * dim_head
         self.use_linear_projection = use_linear_projection
+        # SDXL path: the GroupNorm writes tokens and the closing residual add
+        # reads them (no standalone permute copy, no strided add).
+        # DFA_NO_BOUNDARY_FUSE=1 restores the torch composition (A/B).
+        self.boundary_fuse = (
+            use_linear_projection and os.environ.get("DFA_NO_BOUNDARY_FUSE", "0") != "1"
+        )
         self.norm = factory.group_norm(groups, channels, eps=1e-6, fuse_silu=False)
         if use_linear_projection:
             self.proj_in = nn.Linear(channels, inner)
@@ -87,15 +95,22 @@ class Transformer2DModel(nn.Module):
     def forward(self, x: torch.Tensor, encoder_hidden_states: torch.Tensor) -> torch.Tensor:
         b, c, h, w = x.shape
         residual = x
-        x = self.norm(x)
-        if self.use_linear_projection:
+        if self.boundary_fuse:
+            x = self.norm(x, tokens=True)
+            # proj_in as the permuted view always ran it: F.linear gives a
+            # non-contiguous 3-D input a plain GEMM and adds the bias to the
+            # rounded result. A contiguous input would take the fused-bias GEMM
+            # instead (one rounding, other values); the GEMMs stay as they were.
+            x = torch.matmul(x, self.proj_in.weight.t()).add_(self.proj_in.bias)
+        elif self.use_linear_projection:
+            x = self.norm(x)
             x = x.permute(0, 2, 3, 1).reshape(b, h * w, c)
             x = self.proj_in(x)
         else:
+            x = self.norm(x)
             x = self.proj_in(x)
             inner = x.shape[1]
             x = x.permute(0, 2, 3, 1).reshape(b, h * w, inner)
-        import os
         if os.environ.get("DFA_NO_PENDING_CHAIN", "0") == "1":
             for block in self.transformer_blocks:
                 x, p = block(x, encoder_hidden_states, None)
@@ -105,6 +120,8 @@ class Transformer2DModel(nn.Module):
             for block in self.transformer_blocks:
                 x, pending = block(x, encoder_hidden_states, pending)
             x = x + pending
+        if self.boundary_fuse:
+            return ops.tokens_add_nchw(self.proj_out(x), residual)
         if self.use_linear_projection:
             x = self.proj_out(x)
             x = x.reshape(b, h, w, c).permute(0, 3, 1, 2)

@@ -21,6 +21,7 @@ from .dispatch import (
     hip_ext_available,
     layer_norm,
     merge_attention,
+    tokens_add_nchw,
     vae_attention,
 )
 from .norm import PlainGroupNorm
@@ -42,5 +43,6 @@ __all__ = [
     "hip_ext_available",
     "merge_attention",
     "pack_conv3x3_weight",
+    "tokens_add_nchw",
     "vae_attention",
 ]

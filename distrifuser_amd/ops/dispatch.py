@@ -237,7 +237,9 @@ def group_norm_stats(x: torch.Tensor, num_groups: int) -> torch.Tensor:
     return eager.group_norm_stats(x, num_groups)
 
 
-def group_norm_apply(x, mean, meansq, weight, bias, eps, silu=False):
+def group_norm_apply(x, mean, meansq, weight, bias, eps, silu=False, tokens=False):
+    """tokens=True: the same values as [N, H*W, C] contiguous (the kernel
+    writes them in that order; no NCHW result exists in between)."""
     if _use_hip(x):
         n = x.shape[0]
         g = mean.reshape(n, -1).shape[1]
@@ -249,14 +251,39 @@ def group_norm_apply(x, mean, meansq, weight, bias, eps, silu=False):
             bias,
             eps,
             silu,
+            tokens,
         )
-    return eager.group_norm_apply(x, mean, meansq, weight, bias, eps, silu)
+    return eager.group_norm_apply(x, mean, meansq, weight, bias, eps, silu, tokens)
 
 
-def group_norm_silu(x, num_groups, weight, bias, eps, silu=True):
+def group_norm_silu(x, num_groups, weight, bias, eps, silu=True, tokens=False):
     if _use_hip(x):
-        return hip_ext().group_norm_silu(x, num_groups, weight, bias, eps, silu)
-    return eager.group_norm_silu(x, num_groups, weight, bias, eps, silu)
+        return hip_ext().group_norm_silu(x, num_groups, weight, bias, eps, silu, tokens)
+    return eager.group_norm_silu(x, num_groups, weight, bias, eps, silu, tokens)
+
+
+_BOUNDARY_DTYPES = (torch.bfloat16, torch.float16, torch.float32)
+
+
+def tokens_add_nchw(y: torch.Tensor, residual: torch.Tensor) -> torch.Tensor:
+    """y [N, H*W, C] + residual [N, C, H, W] -> [N, C, H, W] contiguous.
+
+    The transformer's closing residual add with the token -> NCHW transpose
+    inside. residual may be a batch or channel slice of a wider tensor; a
+    residual whose (H, W) plane is not contiguous, mixed dtypes and dtypes
+    outside bf16 / fp16 / fp32 take the eager composition.
+    """
+    if (
+        _use_hip(y)
+        and y.dtype in _BOUNDARY_DTYPES
+        and residual.dtype == y.dtype
+        and residual.is_cuda
+        and residual.dim() == 4
+        and (residual.shape[3] <= 1 or residual.stride(3) == 1)
+        and (residual.shape[2] <= 1 or residual.stride(2) == residual.shape[3])
+    ):
+        return hip_ext().tokens_add_nchw(y, residual)
+    return eager.tokens_add_nchw(y, residual)
 
 
 def layer_norm(x, weight, bias, eps):

@@ -74,6 +74,18 @@ def group_norm_stats(x: torch.Tensor, num_groups: int) -> torch.Tensor:
     return torch.stack([mean, meansq], dim=0).reshape(2, n, num_groups, 1, 1, 1).to(x.dtype)
 
 
+def nchw_to_tokens(x: torch.Tensor) -> torch.Tensor:
+    """[N, C, H, W] -> [N, H*W, C] contiguous (the transformer's token layout)."""
+    n, c, h, w = x.shape
+    return x.permute(0, 2, 3, 1).reshape(n, h * w, c).contiguous()
+
+
+def tokens_add_nchw(y: torch.Tensor, residual: torch.Tensor) -> torch.Tensor:
+    """y [N, H*W, C] back to NCHW plus residual [N, C, H, W], contiguous."""
+    n, c, h, w = residual.shape
+    return (y.reshape(n, h, w, c).permute(0, 3, 1, 2) + residual).contiguous()
+
+
 def group_norm_apply(
     x: torch.Tensor,
     mean: torch.Tensor,
@@ -82,6 +94,7 @@ def group_norm_apply(
     bias: torch.Tensor | None,
     eps: float,
     silu: bool = False,
+    tokens: bool = False,
 ) -> torch.Tensor:
     """Normalize x with externally supplied group stats; optionally fuse SiLU.
 
@@ -105,7 +118,8 @@ def group_norm_apply(
         out = out + bias.float().view(1, -1, 1, 1)
     if silu:
         out = F.silu(out)
-    return out.to(x.dtype)
+    out = out.to(x.dtype)
+    return nchw_to_tokens(out) if tokens else out
 
 
 def group_norm_silu(
@@ -115,13 +129,18 @@ def group_norm_silu(
     bias: torch.Tensor | None,
     eps: float,
     silu: bool = True,
+    tokens: bool = False,
 ) -> torch.Tensor:
-    """Plain (single-device) GroupNorm with fused SiLU epilogue."""
+    """Plain (single-device) GroupNorm with fused SiLU epilogue.
+
+    tokens=True returns the same values as [N, H*W, C] contiguous.
+    """
     out = F.group_norm(x.float(), num_groups, None if weight is None else weight.float(),
                        None if bias is None else bias.float(), eps)
     if silu:
         out = F.silu(out)
-    return out.to(x.dtype)
+    out = out.to(x.dtype)
+    return nchw_to_tokens(out) if tokens else out
 
 
 def geglu(hidden: torch.Tensor) -> torch.Tensor:

@@ -15,7 +15,9 @@ class PlainGroupNorm(nn.GroupNorm):
         super().__init__(num_groups, num_channels, eps=eps, affine=affine)
         self.fuse_silu = fuse_silu
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, tokens: bool = False) -> torch.Tensor:
+        """tokens=True returns [N, H*W, C] instead of NCHW (same values)."""
         return dispatch.group_norm_silu(
-            x, self.num_groups, self.weight, self.bias, self.eps, silu=self.fuse_silu
+            x, self.num_groups, self.weight, self.bias, self.eps, silu=self.fuse_silu,
+            tokens=tokens,
         )

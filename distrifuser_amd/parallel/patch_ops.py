@@ -224,20 +224,23 @@ class PatchGroupNorm(nn.Module):
         self._idx = None
         self._buffer_list = None
 
-    def _local(self, x: torch.Tensor) -> torch.Tensor:
+    def _local(self, x: torch.Tensor, tokens: bool = False) -> torch.Tensor:
         return ops.group_norm_silu(
-            x, self.num_groups, self.weight, self.bias, self.eps, silu=self.fuse_silu
+            x, self.num_groups, self.weight, self.bias, self.eps, silu=self.fuse_silu,
+            tokens=tokens,
         )
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, tokens: bool = False) -> torch.Tensor:
+        """tokens=True returns [N, H*W, C] instead of NCHW (same values) on
+        every branch: the apply kernel writes that layout itself."""
         state = self.state
         cfg = state.config
         if not _is_patch_parallel(state):
-            return self._local(x)
+            return self._local(x, tokens)
         mode = cfg.mode
 
         if mode in ("separate_gn", "no_sync"):
-            return self._local(x)
+            return self._local(x, tokens)
 
         if mode in ("sync_gn", "full_sync"):
             # Every-step all-reduce of the stacked [E[x], E[x^2]].
@@ -245,7 +248,8 @@ class PatchGroupNorm(nn.Module):
             dist.all_reduce(stats, op=dist.ReduceOp.SUM, group=cfg.batch_group)
             stats = stats / cfg.n_device_per_batch
             return ops.group_norm_apply(
-                x, stats[0], stats[1], self.weight, self.bias, self.eps, silu=self.fuse_silu
+                x, stats[0], stats[1], self.weight, self.bias, self.eps, silu=self.fuse_silu,
+                tokens=tokens,
             )
 
         assert mode in ("stale_gn", "corrected_async_gn")
@@ -258,9 +262,9 @@ class PatchGroupNorm(nn.Module):
                     self._idx = comm.register_tensor(
                         (2, n, self.num_groups, 1, 1, 1), x.dtype, layer_type="gn"
                     )
-                return self._local(x)
+                return self._local(x, tokens)
             if self._idx is None:
-                return self._local(x)
+                return self._local(x, tokens)
             self._buffer_list = comm.get_buffer_list(self._idx)
 
         comm.wait(self._idx)
@@ -279,7 +283,7 @@ class PatchGroupNorm(nn.Module):
             comm.enqueue(self._idx)  # fresh already staged in-slot
             return ops.group_norm_apply(
                 x, moments[0], moments[1], self.weight, self.bias, self.eps,
-                silu=self.fuse_silu,
+                silu=self.fuse_silu, tokens=tokens,
             )
 
         if state.in_warmup:
@@ -314,7 +318,8 @@ class PatchGroupNorm(nn.Module):
             neg = var < 0
             meansq = torch.where(neg, mean * mean + local_var, meansq)
         return ops.group_norm_apply(
-            x, mean, meansq, self.weight, self.bias, self.eps, silu=self.fuse_silu
+            x, mean, meansq, self.weight, self.bias, self.eps, silu=self.fuse_silu,
+            tokens=tokens,
         )
 
 
