@@ -72,8 +72,7 @@
 //   block row q, columns 4p..4p+3; lane i receives column i, row q in
 //   element q.
 
-#include "common.h"
-#include "kernels.h"
+#include "dispatch.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -790,18 +789,21 @@ __global__ __launch_bounds__(256) void merge_attn_kernel(MergeAttnParams p) {
         p.lse[lse_row] = wsum > 0.f ? m + logf(wsum) : -__builtin_inff();
 }
 
+// the DfaDtype of an element type
+template <typename T>
+constexpr int dtype_of = std::is_same_v<T, bf16_t>  ? DFA_BF16
+                         : std::is_same_v<T, f16_t> ? DFA_F16
+                                                    : DFA_F32;
+
 }  // namespace
 
 void launch_merge_attention(const MergeAttnParams& p, hipStream_t stream) {
     const int64_t total = (int64_t)p.B * p.Lq * p.H * (p.Dh / 8);
     if (total == 0) return;
     const dim3 grid((unsigned)((total + 255) / 256));
-    if (p.out_dtype == DFA_BF16)
-        merge_attn_kernel<DFA_BF16><<<grid, 256, 0, stream>>>(p);
-    else if (p.out_dtype == DFA_F16)
-        merge_attn_kernel<DFA_F16><<<grid, 256, 0, stream>>>(p);
-    else
-        merge_attn_kernel<DFA_F32><<<grid, 256, 0, stream>>>(p);
+    dispatch_dtype(p.out_dtype, [&]<typename T>(std::type_identity<T>) {
+        merge_attn_kernel<dtype_of<T>><<<grid, 256, 0, stream>>>(p);
+    });
 }
 
 namespace {
@@ -826,10 +828,9 @@ void launch_dpad(const FlashAttnLseParams& p, int splits, hipStream_t stream) {
     const dim3 block(NW * WAVE_SIZE);
     const bool off32 = fits_off32<DPAD>(p);
     const std::conditional_t<LSE, FlashAttnLseParams, FlashAttnParams>& kp = p;
-    if (p.Dh == DPAD)
-        flash_attn_kernel<NW, DPAD, true, LSE, F16><<<grid, block, 0, stream>>>(kp, off32);
-    else
-        flash_attn_kernel<NW, DPAD, false, LSE, F16><<<grid, block, 0, stream>>>(kp, off32);
+    dispatch_bool(p.Dh == DPAD, [&]<bool DFULL>(std::bool_constant<DFULL>) {
+        flash_attn_kernel<NW, DPAD, DFULL, LSE, F16><<<grid, block, 0, stream>>>(kp, off32);
+    });
 }
 
 template <bool LSE, bool F16>
@@ -856,13 +857,12 @@ int flash_attention_num_splits(int64_t lkv, int splits) {
 
 void launch_flash_attention(const FlashAttnLseParams& p, int splits, int dtype,
                             hipStream_t stream) {
-    const bool f16 = dtype == DFA_F16;
-    if (p.lse == nullptr && p.o_part == nullptr) {
-        (f16 ? launch_ladder<false, true> : launch_ladder<false, false>)(p, 1, stream);
-    } else {
-        splits = flash_attention_num_splits(p.NC * p.LC, splits);
-        (f16 ? launch_ladder<true, true> : launch_ladder<true, false>)(p, splits, stream);
-    }
+    dispatch_f16(dtype, [&]<bool F16>(std::bool_constant<F16>) {
+        if (p.lse == nullptr && p.o_part == nullptr)
+            launch_ladder<false, F16>(p, 1, stream);
+        else
+            launch_ladder<true, F16>(p, flash_attention_num_splits(p.NC * p.LC, splits), stream);
+    });
 }
 
 // ---- fragment-layout probes (tests/test_ops_gpu.py) ------------------------

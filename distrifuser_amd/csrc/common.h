@@ -188,11 +188,3 @@ __device__ __forceinline__ uint4 transpose8x8_b16(uint4 v, int lane) {
     }
     return uint4{d[0], d[1], d[2], d[3]};
 }
-
-#define DFA_HIP_CHECK(expr)                                                     \
-    do {                                                                        \
-        hipError_t _e = (expr);                                                 \
-        if (_e != hipSuccess) {                                                 \
-            printf("HIP error %s at %s:%d\n", hipGetErrorString(_e), __FILE__, __LINE__); \
-        }                                                                       \
-    } while (0)

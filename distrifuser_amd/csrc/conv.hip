@@ -30,8 +30,7 @@
 // kernel, interior pointer offset into the full latent), :59-112 (halo
 // exchange, zero-pad at true image borders).
 
-#include "common.h"
-#include "kernels.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -445,25 +444,19 @@ void launch_tile(const Conv3x3Params& p, hipStream_t stream) {
         <<<dim3(conv_grid<T>(p).blocks), dim3(T::NW * WAVE_SIZE), 0, stream>>>(p);
 }
 
-template <bool F16>
-void launch_conv3x3_t(const Conv3x3Params& p, int stride, hipStream_t stream) {
-    if (stride != 1) {
-        if (p.pad_lo == 0)
-            launch_tile<ConvS2, F16, 0>(p, stream);
-        else
-            launch_tile<ConvS2, F16>(p, stream);
-    } else if (p.Wo <= 128) {
-        launch_tile<ConvNarrowS1, F16>(p, stream);
-    } else {
-        launch_tile<ConvWideS1, F16>(p, stream);
-    }
-}
-
 }  // namespace
 
 void launch_conv3x3(const Conv3x3Params& p, int stride, int dtype, hipStream_t stream) {
-    if (dtype == DFA_F16)
-        launch_conv3x3_t<true>(p, stride, stream);
-    else
-        launch_conv3x3_t<false>(p, stride, stream);
+    dispatch_f16(dtype, [&]<bool F16>(std::bool_constant<F16>) {
+        if (stride != 1) {
+            if (p.pad_lo == 0)
+                launch_tile<ConvS2, F16, 0>(p, stream);
+            else
+                launch_tile<ConvS2, F16>(p, stream);
+        } else if (p.Wo <= 128) {
+            launch_tile<ConvNarrowS1, F16>(p, stream);
+        } else {
+            launch_tile<ConvWideS1, F16>(p, stream);
+        }
+    });
 }

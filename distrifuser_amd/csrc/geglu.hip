@@ -2,9 +2,7 @@
 // Memory-bound; 16 B/lane vector loads on both halves, erf-exact gelu
 // (matches torch F.gelu default). Reference numerics: ops/eager.py geglu.
 
-#include "common.h"
-#include "kernels.h"
-#include <algorithm>
+#include "dispatch.h"
 
 namespace {
 
@@ -37,25 +35,15 @@ __global__ void geglu_kernel(const T* __restrict__ in, T* __restrict__ out, int6
     }
 }
 
-template <typename T>
-void geglu_t(const void* in, void* out, int64_t rows, int64_t inner, hipStream_t stream) {
-    const bool vec = (inner % VecN<T>::value) == 0;
-    const int block = 256;
-    const int64_t work = rows * inner / (vec ? VecN<T>::value : 1);
-    const int grid = (int)std::min<int64_t>((work + block - 1) / block, 4096);
-    if (vec)
-        geglu_kernel<T, true><<<grid, block, 0, stream>>>((const T*)in, (T*)out, rows, inner);
-    else
-        geglu_kernel<T, false><<<grid, block, 0, stream>>>((const T*)in, (T*)out, rows, inner);
-}
-
 }  // namespace
 
 void launch_geglu(const void* in, void* out, int64_t rows, int64_t inner, int dtype,
                   hipStream_t stream) {
-    switch (dtype) {
-        case DFA_BF16: geglu_t<bf16_t>(in, out, rows, inner, stream); break;
-        case DFA_F16: geglu_t<f16_t>(in, out, rows, inner, stream); break;
-        default: geglu_t<float>(in, out, rows, inner, stream); break;
-    }
+    const int block = 256;
+    dispatch_dtype(dtype, [&]<typename T>(std::type_identity<T>) {
+        dispatch_bool(inner % VecN<T>::value == 0, [&]<bool VEC>(std::bool_constant<VEC>) {
+            const int grid = grid_for(rows * inner / (VEC ? VecN<T>::value : 1), block);
+            geglu_kernel<T, VEC><<<grid, block, 0, stream>>>((const T*)in, (T*)out, rows, inner);
+        });
+    });
 }

@@ -9,9 +9,7 @@
 // G12); each (sample, group) slab is contiguous in NCHW.
 
 #include "boundary_plan.h"
-#include "common.h"
-#include "kernels.h"
-#include <algorithm>
+#include "dispatch.h"
 
 namespace {
 
@@ -60,6 +58,44 @@ __global__ void gn_finalize_kernel(const float* __restrict__ partial, T* __restr
     if (i < 2 * total) out[i] = from_f32<T>(partial[i] * inv_count);
 }
 
+// The GroupNorm arithmetic of every apply kernel, NCHW and token-layout alike:
+// the per-channel scale / shift and the per-element value, each rounding step
+// spelled out with contraction off, so the result is a property of this source
+// and not of where an optimiser chooses to form fmas. There are two forms.
+// FUSED takes `m * sc` and `x * sc` into fmas; the other rounds each product
+// first. gn_fused() on the host picks the form from the tensor alone, so the
+// NCHW kernel and both token tile paths give the same bits for the same tensor
+// (tests/test_transformer_boundary_gpu.py holds them to that).
+template <bool FUSED>
+__device__ __forceinline__ void gn_scale_shift(float m, float msq, float eps, float wv, float bv,
+                                               float& sc, float& sh) {
+#pragma clang fp contract(off)  // every fma below is spelled out
+    float var = __builtin_fmaf(-m, m, msq);
+    var = var < 0.f ? 0.f : var;
+    const float inv = rsqrtf(var + eps);
+    sc = wv * inv;
+    if (FUSED) {
+        sh = __builtin_fmaf(-m, sc, bv);
+    } else {
+        const float ms = m * sc;
+        sh = bv - ms;
+    }
+}
+template <bool FUSED>
+__device__ __forceinline__ float gn_norm(float x, float sc, float sh) {
+#pragma clang fp contract(off)
+    if (FUSED) return __builtin_fmaf(x, sc, sh);
+    const float xs = x * sc;
+    return xs + sh;
+}
+
+// Fused arithmetic iff HW is a whole number of 16-byte vectors: the tensors the
+// NCHW kernel takes with vector accesses. The only place that decides the form.
+template <typename T>
+bool gn_fused(int64_t hw) {
+    return hw % VecN<T>::value == 0;
+}
+
 template <typename T, bool SILU, bool VEC>
 __global__ void gn_apply_kernel(const T* __restrict__ x, T* __restrict__ y,
                                 const float* __restrict__ mean, const float* __restrict__ meansq,
@@ -74,12 +110,9 @@ __global__ void gn_apply_kernel(const T* __restrict__ x, T* __restrict__ y,
         const int64_t c = (i / hw) % C;
         const int64_t n = i / (hw * (int64_t)C);
         const int g = (int)(c / gs);
-        const float m = mean[n * G + g];
-        float var = meansq[n * G + g] - m * m;
-        var = var < 0.f ? 0.f : var;
-        const float inv = rsqrtf(var + eps);
-        const float sc = (w ? to_f32(w[c]) : 1.f) * inv;
-        const float sh = (b ? to_f32(b[c]) : 0.f) - m * sc;
+        float sc, sh;  // VEC is also the arithmetic form: gn_fused() chose both
+        gn_scale_shift<VEC>(mean[n * G + g], meansq[n * G + g], eps, w ? to_f32(w[c]) : 1.f,
+                            b ? to_f32(b[c]) : 0.f, sc, sh);
         if (VEC) {
             uint4 raw = *reinterpret_cast<const uint4*>(x + i);
             const T* e = reinterpret_cast<const T*>(&raw);
@@ -87,67 +120,16 @@ __global__ void gn_apply_kernel(const T* __restrict__ x, T* __restrict__ y,
             T* o = reinterpret_cast<T*>(&outv);
 #pragma unroll
             for (int j = 0; j < V; ++j) {
-                float f = to_f32(e[j]) * sc + sh;
+                float f = gn_norm<VEC>(to_f32(e[j]), sc, sh);
                 if (SILU) f = siluf(f);
                 o[j] = from_f32<T>(f);
             }
             *reinterpret_cast<uint4*>(y + i) = outv;
         } else {
-            float f = to_f32(x[i]) * sc + sh;
+            float f = gn_norm<VEC>(to_f32(x[i]), sc, sh);
             if (SILU) f = siluf(f);
             y[i] = from_f32<T>(f);
         }
-    }
-}
-
-inline int grid_for(int64_t work, int block) {
-    int64_t g = (work + block - 1) / block;
-    return (int)std::min<int64_t>(g, 4096);
-}
-
-template <typename T>
-void gn_stats_partial_t(const void* x, float* partial, int64_t group_len, int ngt,
-                        hipStream_t stream) {
-    // size chunks so the chip is filled: >= 2048 blocks total
-    const bool vec = (group_len % VecN<T>::value) == 0;
-    const int V = vec ? VecN<T>::value : 1;
-    int chunks = (int)std::max<int64_t>(1, (2048 + ngt - 1) / ngt);
-    // but never more chunks than work
-    int64_t nvec = std::max<int64_t>(group_len / V, 1);
-    chunks = (int)std::min<int64_t>(chunks, (nvec + 255) / 256);
-    chunks = std::max(chunks, 1);
-    dim3 grid(ngt * chunks);
-    if (vec)
-        gn_stats_partial_kernel<T, true><<<grid, 256, 0, stream>>>(
-            reinterpret_cast<const T*>(x), partial, group_len, chunks, ngt);
-    else
-        gn_stats_partial_kernel<T, false><<<grid, 256, 0, stream>>>(
-            reinterpret_cast<const T*>(x), partial, group_len, chunks, ngt);
-}
-
-template <typename T>
-void gn_apply_t(const void* x, void* y, const float* mean, const float* meansq, const void* w,
-                const void* b, float eps, int64_t hw, int C, int G, int N, bool silu,
-                hipStream_t stream) {
-    const int64_t total = (int64_t)N * C * hw;
-    const bool vec = (hw % VecN<T>::value) == 0;
-    const int block = 256;
-    if (vec) {
-        int grid = grid_for(total / VecN<T>::value, block);
-        if (silu)
-            gn_apply_kernel<T, true, true><<<grid, block, 0, stream>>>(
-                (const T*)x, (T*)y, mean, meansq, (const T*)w, (const T*)b, eps, hw, C, G, total);
-        else
-            gn_apply_kernel<T, false, true><<<grid, block, 0, stream>>>(
-                (const T*)x, (T*)y, mean, meansq, (const T*)w, (const T*)b, eps, hw, C, G, total);
-    } else {
-        int grid = grid_for(total, block);
-        if (silu)
-            gn_apply_kernel<T, true, false><<<grid, block, 0, stream>>>(
-                (const T*)x, (T*)y, mean, meansq, (const T*)w, (const T*)b, eps, hw, C, G, total);
-        else
-            gn_apply_kernel<T, false, false><<<grid, block, 0, stream>>>(
-                (const T*)x, (T*)y, mean, meansq, (const T*)w, (const T*)b, eps, hw, C, G, total);
     }
 }
 
@@ -179,37 +161,6 @@ __device__ __forceinline__ int bt_chunk(int prow, int q) {
 template <typename T>
 __device__ __forceinline__ uint32_t bits16(T v) {
     return (uint32_t)__builtin_bit_cast(uint16_t, v);
-}
-
-// The per-channel scale / shift and the per-element value of gn_apply_kernel,
-// with its floating-point contraction written out. The compiler fuses
-// gn_apply_kernel's `m * sc` and `x * sc` into fmas in its vector variants and
-// keeps them as a multiply and an add / subtract in its scalar variants (there
-// it pairs the two multiplies into one packed instruction). FUSED says which
-// of the two the NCHW kernel takes for the same tensor (HW % VecN == 0), so a
-// token-layout result is bit-identical to the NCHW one whichever tile path
-// produces it (tests/test_transformer_boundary_gpu.py holds both to that).
-template <bool FUSED>
-__device__ __forceinline__ void gn_scale_shift(float m, float msq, float eps, float wv, float bv,
-                                               float& sc, float& sh) {
-#pragma clang fp contract(off)  // every fma below is spelled out
-    float var = __builtin_fmaf(-m, m, msq);
-    var = var < 0.f ? 0.f : var;
-    const float inv = rsqrtf(var + eps);
-    sc = wv * inv;
-    if (FUSED) {
-        sh = __builtin_fmaf(-m, sc, bv);
-    } else {
-        const float ms = m * sc;
-        sh = bv - ms;
-    }
-}
-template <bool FUSED>
-__device__ __forceinline__ float gn_norm(float x, float sc, float sh) {
-#pragma clang fp contract(off)
-    if (FUSED) return __builtin_fmaf(x, sc, sh);
-    const float xs = x * sc;
-    return xs + sh;
 }
 
 template <typename T, bool SILU>
@@ -387,60 +338,6 @@ __global__ __launch_bounds__(BOUNDARY_THREADS) void tokens_add_nchw_scalar_kerne
     }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-template <typename T>
-void gn_apply_tokens_t(const void* x, void* y, const float* mean, const float* meansq,
-                       const void* w, const void* b, float eps, int64_t hw, int C, int G, int N,
-                       bool silu, hipStream_t stream) {
-    const BoundaryPlan pl =
-        boundary_plan(N, C, hw, (int)sizeof(T), aligned16(x) && aligned16(y));
-    if (!pl.ok) return;  // empty; the binding rejects an oversized grid
-    const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y, (unsigned)pl.grid_z);
-#define DFA_GN_TOKENS_LAUNCH(...)                                                            \
-    __VA_ARGS__<<<grid, BOUNDARY_THREADS, 0, stream>>>((const T*)x, (T*)y, mean, meansq,     \
-                                                       (const T*)w, (const T*)b, eps, hw, C, G)
-    if constexpr (sizeof(T) == 2) {
-        if (pl.vec) {
-            if (silu)
-                DFA_GN_TOKENS_LAUNCH(gn_apply_tokens_vec_kernel<T, true>);
-            else
-                DFA_GN_TOKENS_LAUNCH(gn_apply_tokens_vec_kernel<T, false>);
-            return;
-        }
-    }
-    // the arithmetic form of the NCHW kernel for this tensor (gn_apply_t's choice)
-    const bool fused = (hw % VecN<T>::value) == 0;
-    if (silu && fused)
-        DFA_GN_TOKENS_LAUNCH(gn_apply_tokens_scalar_kernel<T, true, true>);
-    else if (silu)
-        DFA_GN_TOKENS_LAUNCH(gn_apply_tokens_scalar_kernel<T, true, false>);
-    else if (fused)
-        DFA_GN_TOKENS_LAUNCH(gn_apply_tokens_scalar_kernel<T, false, true>);
-    else
-        DFA_GN_TOKENS_LAUNCH(gn_apply_tokens_scalar_kernel<T, false, false>);
-#undef DFA_GN_TOKENS_LAUNCH
-}
-
-template <typename T>
-void tokens_add_nchw_t(const void* y, const void* res, void* out, int64_t hw, int C, int N,
-                       int64_t rs_n, int64_t rs_c, hipStream_t stream) {
-    const bool al = aligned16(y) && aligned16(res) && aligned16(out) && rs_n % 8 == 0 &&
-                    rs_c % 8 == 0;
-    const BoundaryPlan pl = boundary_plan(N, C, hw, (int)sizeof(T), al);
-    if (!pl.ok) return;
-    const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y, (unsigned)pl.grid_z);
-    if constexpr (sizeof(T) == 2) {
-        if (pl.vec) {
-            tokens_add_nchw_vec_kernel<T><<<grid, BOUNDARY_THREADS, 0, stream>>>(
-                (const T*)y, (const T*)res, (T*)out, hw, C, rs_n, rs_c);
-            return;
-        }
-    }
-    tokens_add_nchw_scalar_kernel<T><<<grid, BOUNDARY_THREADS, 0, stream>>>(
-        (const T*)y, (const T*)res, (T*)out, hw, C, rs_n, rs_c);
-}
-
 template <typename T, bool CORRECTED>
 __global__ void gn_merge_stats_kernel(T* __restrict__ buffer, int64_t row_stride,
                                       int64_t slot_off, int n_peers, int own,
@@ -486,6 +383,8 @@ __global__ void gn_merge_stats_kernel(T* __restrict__ buffer, int64_t row_stride
     own_slot[ng + g] = fresh[ng + g];
 }
 
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 }  // namespace
 
 void launch_gn_merge_stats(void* buffer, int64_t row_stride, int64_t slot_off, int n_peers,
@@ -493,117 +392,100 @@ void launch_gn_merge_stats(void* buffer, int64_t row_stride, int64_t slot_off, i
                            int dtype, hipStream_t stream) {
     const int block = 256;
     const int grid = (ng + block - 1) / block;
-    switch (dtype) {
-        case DFA_BF16:
-            if (corrected)
-                gn_merge_stats_kernel<bf16_t, true><<<grid, block, 0, stream>>>(
-                    (bf16_t*)buffer, row_stride, slot_off, n_peers, own, (const bf16_t*)fresh,
-                    out, ng);
-            else
-                gn_merge_stats_kernel<bf16_t, false><<<grid, block, 0, stream>>>(
-                    (bf16_t*)buffer, row_stride, slot_off, n_peers, own, (const bf16_t*)fresh,
-                    out, ng);
-            break;
-        case DFA_F16:
-            if (corrected)
-                gn_merge_stats_kernel<f16_t, true><<<grid, block, 0, stream>>>(
-                    (f16_t*)buffer, row_stride, slot_off, n_peers, own, (const f16_t*)fresh,
-                    out, ng);
-            else
-                gn_merge_stats_kernel<f16_t, false><<<grid, block, 0, stream>>>(
-                    (f16_t*)buffer, row_stride, slot_off, n_peers, own, (const f16_t*)fresh,
-                    out, ng);
-            break;
-        default:
-            if (corrected)
-                gn_merge_stats_kernel<float, true><<<grid, block, 0, stream>>>(
-                    (float*)buffer, row_stride, slot_off, n_peers, own, (const float*)fresh,
-                    out, ng);
-            else
-                gn_merge_stats_kernel<float, false><<<grid, block, 0, stream>>>(
-                    (float*)buffer, row_stride, slot_off, n_peers, own, (const float*)fresh,
-                    out, ng);
-            break;
-    }
+    dispatch_dtype(dtype, [&]<typename T>(std::type_identity<T>) {
+        dispatch_bool(corrected, [&]<bool CORRECTED>(std::bool_constant<CORRECTED>) {
+            gn_merge_stats_kernel<T, CORRECTED><<<grid, block, 0, stream>>>(
+                (T*)buffer, row_stride, slot_off, n_peers, own, (const T*)fresh, out, ng);
+        });
+    });
 }
 
 void launch_gn_stats_partial(const void* x, float* partial, int64_t group_len, int ngt, int dtype,
                              hipStream_t stream) {
-    switch (dtype) {
-        case DFA_BF16: gn_stats_partial_t<bf16_t>(x, partial, group_len, ngt, stream); break;
-        case DFA_F16: gn_stats_partial_t<f16_t>(x, partial, group_len, ngt, stream); break;
-        default: gn_stats_partial_t<float>(x, partial, group_len, ngt, stream); break;
-    }
+    dispatch_dtype(dtype, [&]<typename T>(std::type_identity<T>) {
+        dispatch_bool(group_len % VecN<T>::value == 0, [&]<bool VEC>(std::bool_constant<VEC>) {
+            // size chunks so the chip is filled: >= 2048 blocks total
+            constexpr int V = VEC ? VecN<T>::value : 1;
+            int chunks = (int)std::max<int64_t>(1, (2048 + ngt - 1) / ngt);
+            // but never more chunks than work
+            int64_t nvec = std::max<int64_t>(group_len / V, 1);
+            chunks = (int)std::min<int64_t>(chunks, (nvec + 255) / 256);
+            chunks = std::max(chunks, 1);
+            gn_stats_partial_kernel<T, VEC><<<dim3(ngt * chunks), 256, 0, stream>>>(
+                (const T*)x, partial, group_len, chunks, ngt);
+        });
+    });
 }
 
 void launch_gn_finalize(const float* partial, void* out, float inv_count, int ngt, int dtype,
                         hipStream_t stream) {
-    int total = 2 * ngt;
-    int block = 256;
-    int grid = (total + block - 1) / block;
-    switch (dtype) {
-        case DFA_BF16:
-            gn_finalize_kernel<bf16_t><<<grid, block, 0, stream>>>(partial, (bf16_t*)out, inv_count, ngt);
-            break;
-        case DFA_F16:
-            gn_finalize_kernel<f16_t><<<grid, block, 0, stream>>>(partial, (f16_t*)out, inv_count, ngt);
-            break;
-        default:
-            gn_finalize_kernel<float><<<grid, block, 0, stream>>>(partial, (float*)out, inv_count, ngt);
-            break;
-    }
+    const int block = 256;
+    const int grid = (2 * ngt + block - 1) / block;
+    dispatch_dtype(dtype, [&]<typename T>(std::type_identity<T>) {
+        gn_finalize_kernel<T><<<grid, block, 0, stream>>>(partial, (T*)out, inv_count, ngt);
+    });
 }
 
 void launch_gn_apply(const void* x, void* y, const float* mean, const float* meansq,
                      const void* weight, const void* bias, float eps, int64_t hw, int C, int G,
                      int N, bool silu, int dtype, hipStream_t stream) {
-    switch (dtype) {
-        case DFA_BF16:
-            gn_apply_t<bf16_t>(x, y, mean, meansq, weight, bias, eps, hw, C, G, N, silu, stream);
-            break;
-        case DFA_F16:
-            gn_apply_t<f16_t>(x, y, mean, meansq, weight, bias, eps, hw, C, G, N, silu, stream);
-            break;
-        default:
-            gn_apply_t<float>(x, y, mean, meansq, weight, bias, eps, hw, C, G, N, silu, stream);
-            break;
-    }
+    const int64_t total = (int64_t)N * C * hw;
+    const int block = 256;
+    dispatch_dtype(dtype, [&]<typename T>(std::type_identity<T>) {
+        dispatch_bool(gn_fused<T>(hw), [&]<bool VEC>(std::bool_constant<VEC>) {
+            const int grid = grid_for(total / (VEC ? VecN<T>::value : 1), block);
+            dispatch_bool(silu, [&]<bool SILU>(std::bool_constant<SILU>) {
+                gn_apply_kernel<T, SILU, VEC><<<grid, block, 0, stream>>>(
+                    (const T*)x, (T*)y, mean, meansq, (const T*)weight, (const T*)bias, eps, hw,
+                    C, G, total);
+            });
+        });
+    });
 }
 
 void launch_gn_apply_tokens(const void* x, void* y, const float* mean, const float* meansq,
                             const void* weight, const void* bias, float eps, int64_t hw, int C,
                             int G, int N, bool silu, int dtype, hipStream_t stream) {
-    switch (dtype) {
-        case DFA_BF16:
-            gn_apply_tokens_t<bf16_t>(x, y, mean, meansq, weight, bias, eps, hw, C, G, N, silu,
-                                      stream);
-            break;
-        case DFA_F16:
-            gn_apply_tokens_t<f16_t>(x, y, mean, meansq, weight, bias, eps, hw, C, G, N, silu,
-                                     stream);
-            break;
-        default:
-            gn_apply_tokens_t<float>(x, y, mean, meansq, weight, bias, eps, hw, C, G, N, silu,
-                                     stream);
-            break;
-    }
+    dispatch_dtype(dtype, [&]<typename T>(std::type_identity<T>) {
+        const BoundaryPlan pl =
+            boundary_plan(N, C, hw, (int)sizeof(T), aligned16(x) && aligned16(y));
+        if (!pl.ok) return;  // empty; the binding rejects an oversized grid
+        const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y, (unsigned)pl.grid_z);
+        dispatch_bool(silu, [&]<bool SILU>(std::bool_constant<SILU>) {
+            // one argument list for the three kernels
+            const auto launch = [&](auto kernel) {
+                kernel<<<grid, BOUNDARY_THREADS, 0, stream>>>((const T*)x, (T*)y, mean, meansq,
+                                                              (const T*)weight, (const T*)bias,
+                                                              eps, hw, C, G);
+            };
+            if constexpr (sizeof(T) == 2) {
+                if (pl.vec) return launch(gn_apply_tokens_vec_kernel<T, SILU>);
+            }
+            if (gn_fused<T>(hw))
+                launch(gn_apply_tokens_scalar_kernel<T, SILU, true>);
+            else
+                launch(gn_apply_tokens_scalar_kernel<T, SILU, false>);
+        });
+    });
 }
 
 void launch_tokens_add_nchw(const void* y, const void* residual, void* out, int64_t hw, int C,
                             int N, int64_t res_stride_n, int64_t res_stride_c, int dtype,
                             hipStream_t stream) {
-    switch (dtype) {
-        case DFA_BF16:
-            tokens_add_nchw_t<bf16_t>(y, residual, out, hw, C, N, res_stride_n, res_stride_c,
-                                      stream);
-            break;
-        case DFA_F16:
-            tokens_add_nchw_t<f16_t>(y, residual, out, hw, C, N, res_stride_n, res_stride_c,
-                                     stream);
-            break;
-        default:
-            tokens_add_nchw_t<float>(y, residual, out, hw, C, N, res_stride_n, res_stride_c,
-                                     stream);
-            break;
-    }
+    dispatch_dtype(dtype, [&]<typename T>(std::type_identity<T>) {
+        const bool al = aligned16(y) && aligned16(residual) && aligned16(out) &&
+                        res_stride_n % 8 == 0 && res_stride_c % 8 == 0;
+        const BoundaryPlan pl = boundary_plan(N, C, hw, (int)sizeof(T), al);
+        if (!pl.ok) return;
+        const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y, (unsigned)pl.grid_z);
+        const auto launch = [&](auto kernel) {
+            kernel<<<grid, BOUNDARY_THREADS, 0, stream>>>((const T*)y, (const T*)residual,
+                                                          (T*)out, hw, C, res_stride_n,
+                                                          res_stride_c);
+        };
+        if constexpr (sizeof(T) == 2) {
+            if (pl.vec) return launch(tokens_add_nchw_vec_kernel<T>);
+        }
+        launch(tokens_add_nchw_scalar_kernel<T>);
+    });
 }

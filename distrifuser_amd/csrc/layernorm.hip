@@ -7,8 +7,7 @@
 // the sum also written out — so the transformer block's `x = x + attn(...)`
 // add never runs as a separate elementwise kernel.
 
-#include "common.h"
-#include "kernels.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -84,10 +83,9 @@ __global__ __launch_bounds__(WPB* WAVE_SIZE) void ln_kernel(
 
 }  // namespace
 
-template <bool F16>
-static void launch_layer_norm_t(const void* x, const void* res, void* y, void* sum_out,
-                                const void* w, const void* b, float eps, int64_t rows, int C,
-                                hipStream_t stream) {
+void launch_layer_norm(const void* x, const void* res, void* y, void* sum_out,
+                       const void* w, const void* b, float eps, int64_t rows, int C,
+                       int dtype, hipStream_t stream) {
     dim3 grid((unsigned)((rows + WPB - 1) / WPB));
     dim3 block(WPB * WAVE_SIZE);
     const auto* xp = reinterpret_cast<const uint16_t*>(x);
@@ -96,21 +94,14 @@ static void launch_layer_norm_t(const void* x, const void* res, void* y, void* s
     auto* sp = reinterpret_cast<uint16_t*>(sum_out);
     const auto* wp = reinterpret_cast<const uint16_t*>(w);
     const auto* bp = reinterpret_cast<const uint16_t*>(b);
-    if (C <= 512)
-        ln_kernel<1, F16><<<grid, block, 0, stream>>>(xp, rp, yp, sp, wp, bp, eps, rows, C);
-    else if (C <= 1024)
-        ln_kernel<2, F16><<<grid, block, 0, stream>>>(xp, rp, yp, sp, wp, bp, eps, rows, C);
-    else if (C <= 1536)
-        ln_kernel<3, F16><<<grid, block, 0, stream>>>(xp, rp, yp, sp, wp, bp, eps, rows, C);
-    else
-        ln_kernel<4, F16><<<grid, block, 0, stream>>>(xp, rp, yp, sp, wp, bp, eps, rows, C);
-}
-
-void launch_layer_norm(const void* x, const void* res, void* y, void* sum_out,
-                       const void* w, const void* b, float eps, int64_t rows, int C,
-                       int dtype, hipStream_t stream) {
-    if (dtype == DFA_F16)
-        launch_layer_norm_t<true>(x, res, y, sum_out, w, b, eps, rows, C, stream);
-    else
-        launch_layer_norm_t<false>(x, res, y, sum_out, w, b, eps, rows, C, stream);
+    dispatch_f16(dtype, [&]<bool F16>(std::bool_constant<F16>) {
+        if (C <= 512)
+            ln_kernel<1, F16><<<grid, block, 0, stream>>>(xp, rp, yp, sp, wp, bp, eps, rows, C);
+        else if (C <= 1024)
+            ln_kernel<2, F16><<<grid, block, 0, stream>>>(xp, rp, yp, sp, wp, bp, eps, rows, C);
+        else if (C <= 1536)
+            ln_kernel<3, F16><<<grid, block, 0, stream>>>(xp, rp, yp, sp, wp, bp, eps, rows, C);
+        else
+            ln_kernel<4, F16><<<grid, block, 0, stream>>>(xp, rp, yp, sp, wp, bp, eps, rows, C);
+    });
 }

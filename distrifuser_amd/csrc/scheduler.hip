@@ -10,8 +10,7 @@
 // Euler: ca = 1,                cb = sigma_next - sigma
 // Reference numerics: schedulers/{ddim,euler}.py + pipelines._denoise.
 
-#include "common.h"
-#include "kernels.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -49,37 +48,19 @@ __global__ void cfg_affine_step_kernel(const T* __restrict__ noise_u,
     }
 }
 
-template <typename T>
-void affine_t(const void* nu, const void* nc, const void* x, void* out, float g, float ca,
-              float cb, int64_t total, hipStream_t stream) {
-    const bool vec = (total % VecN<T>::value) == 0;
-    const int block = 256;
-    const int64_t work = total / (vec ? VecN<T>::value : 1);
-    const int grid = (int)((work + block - 1) / block < 4096 ? (work + block - 1) / block : 4096);
-    if (vec)
-        cfg_affine_step_kernel<T, true><<<grid, block, 0, stream>>>(
-            (const T*)nu, (const T*)nc, (const T*)x, (T*)out, g, ca, cb, total);
-    else
-        cfg_affine_step_kernel<T, false><<<grid, block, 0, stream>>>(
-            (const T*)nu, (const T*)nc, (const T*)x, (T*)out, g, ca, cb, total);
-}
-
 }  // namespace
 
 void launch_cfg_affine_step(const void* noise_u, const void* noise_c, const void* x, void* out,
                             float g, float ca, float cb, int64_t total, int dtype,
                             hipStream_t stream) {
-    switch (dtype) {
-        case DFA_BF16:
-            affine_t<bf16_t>(noise_u, noise_c, x, out, g, ca, cb, total, stream);
-            break;
-        case DFA_F16:
-            affine_t<f16_t>(noise_u, noise_c, x, out, g, ca, cb, total, stream);
-            break;
-        default:
-            affine_t<float>(noise_u, noise_c, x, out, g, ca, cb, total, stream);
-            break;
-    }
+    const int block = 256;
+    dispatch_dtype(dtype, [&]<typename T>(std::type_identity<T>) {
+        dispatch_bool(total % VecN<T>::value == 0, [&]<bool VEC>(std::bool_constant<VEC>) {
+            const int grid = grid_for(total / (VEC ? VecN<T>::value : 1), block);
+            cfg_affine_step_kernel<T, VEC><<<grid, block, 0, stream>>>(
+                (const T*)noise_u, (const T*)noise_c, (const T*)x, (T*)out, g, ca, cb, total);
+        });
+    });
 }
 
 namespace {
@@ -112,21 +93,10 @@ void launch_cfg_dpm_step(const void* nu, const void* nc, const void* x, const vo
                          void* out, void* x0_out, float g, float ca, float cb, float cc,
                          float cx, float ce, int64_t total, int dtype, hipStream_t stream) {
     const int block = 256;
-    const int grid = (int)((total + block - 1) / block < 4096 ? (total + block - 1) / block : 4096);
-    switch (dtype) {
-        case DFA_BF16:
-            cfg_dpm_step_kernel<bf16_t><<<grid, block, 0, stream>>>(
-                (const bf16_t*)nu, (const bf16_t*)nc, (const bf16_t*)x, (const float*)x0_prev,
-                (bf16_t*)out, (float*)x0_out, g, ca, cb, cc, cx, ce, total);
-            break;
-        case DFA_F16:
-            cfg_dpm_step_kernel<f16_t><<<grid, block, 0, stream>>>(
-                (const f16_t*)nu, (const f16_t*)nc, (const f16_t*)x, (const float*)x0_prev,
-                (f16_t*)out, (float*)x0_out, g, ca, cb, cc, cx, ce, total);
-            break;
-        default:
-            cfg_dpm_step_kernel<float><<<grid, block, 0, stream>>>(
-                (const float*)nu, (const float*)nc, (const float*)x, (const float*)x0_prev,
-                (float*)out, (float*)x0_out, g, ca, cb, cc, cx, ce, total);
-    }
+    const int grid = grid_for(total, block);
+    dispatch_dtype(dtype, [&]<typename T>(std::type_identity<T>) {
+        cfg_dpm_step_kernel<T><<<grid, block, 0, stream>>>(
+            (const T*)nu, (const T*)nc, (const T*)x, (const float*)x0_prev, (T*)out,
+            (float*)x0_out, g, ca, cb, cc, cx, ce, total);
+    });
 }

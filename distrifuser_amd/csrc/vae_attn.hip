@@ -22,8 +22,7 @@
 // Replaces the chunked bf16 einsum fallback in models/vae.py, which
 // materialized fp32 score slabs.
 
-#include "common.h"
-#include "kernels.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -247,8 +246,7 @@ __global__ __launch_bounds__(NW * WAVE_SIZE) void vae_attn_kernel(VaeAttnParams 
 
 void launch_vae_attention(const VaeAttnParams& p, int dtype, hipStream_t stream) {
     dim3 grid((unsigned)((p.L + QT - 1) / QT), (unsigned)p.B);
-    if (dtype == DFA_F16)
-        vae_attn_kernel<true><<<grid, dim3(NW * WAVE_SIZE), 0, stream>>>(p);
-    else
-        vae_attn_kernel<false><<<grid, dim3(NW * WAVE_SIZE), 0, stream>>>(p);
+    dispatch_f16(dtype, [&]<bool F16>(std::bool_constant<F16>) {
+        vae_attn_kernel<F16><<<grid, dim3(NW * WAVE_SIZE), 0, stream>>>(p);
+    });
 }

@@ -22,6 +22,7 @@ from .dispatch import (
     layer_norm,
     merge_attention,
     tokens_add_nchw,
+    use_hip,
     vae_attention,
 )
 from .norm import PlainGroupNorm
@@ -44,5 +45,6 @@ __all__ = [
     "merge_attention",
     "pack_conv3x3_weight",
     "tokens_add_nchw",
+    "use_hip",
     "vae_attention",
 ]

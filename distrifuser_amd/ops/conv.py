@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from . import eager
-from .dispatch import _use_hip, hip_ext
+from .dispatch import use_hip, hip_ext
 
 
 _CONV_DTYPES = (torch.bfloat16, torch.float16)
@@ -72,7 +72,7 @@ def conv3x3_halo(x, weight, bias, stride=1, top=None, bot=None, packed=None, res
         out = conv3x3_halo(x, weight, bias, stride, top, bot, packed=packed, bias2=bias2,
                            pad_lo=pad_lo)
         return out + residual
-    if _use_hip(x) and packed is not None and _hip_conv_ok(x, stride):
+    if use_hip(x) and packed is not None and _hip_conv_ok(x, stride):
         cout = weight.shape[0]
         t = top.reshape(top.shape[0], top.shape[1], -1) if top is not None else None
         b = bot.reshape(bot.shape[0], bot.shape[1], -1) if bot is not None else None

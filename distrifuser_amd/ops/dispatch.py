@@ -45,7 +45,8 @@ def hip_ext_available() -> bool:
         return False
 
 
-def _use_hip(x: torch.Tensor) -> bool:
+def use_hip(x: torch.Tensor) -> bool:
+    """The one native-or-eager decision: a GPU tensor, DFA_FORCE_EAGER not 1."""
     return x.is_cuda and not _force_eager()
 
 
@@ -95,7 +96,7 @@ def flash_attention(
     eager path accepts kv_splits and ignores it.
     """
     _check_kv_splits(kv_splits)
-    if _use_hip(q) and _flash_ok(q, k, v):
+    if use_hip(q) and _flash_ok(q, k, v):
         if kv_splits == 1 and not return_lse:
             return hip_ext().flash_attention(q, k, v)
         res = hip_ext().flash_attention_ext(q, k, v, kv_splits, return_lse)
@@ -118,7 +119,7 @@ def flash_attention_chunked(
     _check_kv_splits(kv_splits)
     b, lq, inner = q.shape
     n, _, l, _ = kv_chunks.shape
-    if _use_hip(q):
+    if use_hip(q):
         q4 = q.view(b, lq, heads, dim_head).permute(0, 2, 1, 3)
         k = kv_chunks[..., :inner].unflatten(-1, (heads, dim_head)).permute(1, 3, 0, 2, 4)
         v = kv_chunks[..., inner:].unflatten(-1, (heads, dim_head)).permute(1, 3, 0, 2, 4)
@@ -155,7 +156,7 @@ def merge_attention(
     """
     dt = o_parts.dtype if out_dtype is None else out_dtype
     if (
-        _use_hip(o_parts)
+        use_hip(o_parts)
         and o_parts.dtype == torch.float32
         and lse_parts.dtype == torch.float32
         and dt in (torch.bfloat16, torch.float16, torch.float32)
@@ -232,7 +233,7 @@ def attention_kv_splits(
 
 
 def group_norm_stats(x: torch.Tensor, num_groups: int) -> torch.Tensor:
-    if _use_hip(x):
+    if use_hip(x):
         return hip_ext().group_norm_stats(x, num_groups)
     return eager.group_norm_stats(x, num_groups)
 
@@ -240,7 +241,7 @@ def group_norm_stats(x: torch.Tensor, num_groups: int) -> torch.Tensor:
 def group_norm_apply(x, mean, meansq, weight, bias, eps, silu=False, tokens=False):
     """tokens=True: the same values as [N, H*W, C] contiguous (the kernel
     writes them in that order; no NCHW result exists in between)."""
-    if _use_hip(x):
+    if use_hip(x):
         n = x.shape[0]
         g = mean.reshape(n, -1).shape[1]
         return hip_ext().group_norm_apply(
@@ -257,7 +258,7 @@ def group_norm_apply(x, mean, meansq, weight, bias, eps, silu=False, tokens=Fals
 
 
 def group_norm_silu(x, num_groups, weight, bias, eps, silu=True, tokens=False):
-    if _use_hip(x):
+    if use_hip(x):
         return hip_ext().group_norm_silu(x, num_groups, weight, bias, eps, silu, tokens)
     return eager.group_norm_silu(x, num_groups, weight, bias, eps, silu, tokens)
 
@@ -274,7 +275,7 @@ def tokens_add_nchw(y: torch.Tensor, residual: torch.Tensor) -> torch.Tensor:
     outside bf16 / fp16 / fp32 take the eager composition.
     """
     if (
-        _use_hip(y)
+        use_hip(y)
         and y.dtype in _BOUNDARY_DTYPES
         and residual.dtype == y.dtype
         and residual.is_cuda
@@ -287,14 +288,14 @@ def tokens_add_nchw(y: torch.Tensor, residual: torch.Tensor) -> torch.Tensor:
 
 
 def layer_norm(x, weight, bias, eps):
-    if _use_hip(x) and x.dtype in _KERNEL_DTYPES and x.shape[-1] % 8 == 0 and x.shape[-1] <= 2048:
+    if use_hip(x) and x.dtype in _KERNEL_DTYPES and x.shape[-1] % 8 == 0 and x.shape[-1] <= 2048:
         return hip_ext().layer_norm(x, weight, bias, eps)
     return eager.layer_norm(x, weight, bias, eps)
 
 
 def add_layer_norm(x, res, weight, bias, eps):
     """(x + res, LN(x + res)) in one kernel on GPU."""
-    if _use_hip(x) and x.dtype in _KERNEL_DTYPES and x.shape[-1] % 8 == 0 and x.shape[-1] <= 2048:
+    if use_hip(x) and x.dtype in _KERNEL_DTYPES and x.shape[-1] % 8 == 0 and x.shape[-1] <= 2048:
         s, y = hip_ext().add_layer_norm(x, res, weight, bias, eps)
         return s, y
     return eager.add_layer_norm(x, res, weight, bias, eps)
@@ -302,12 +303,12 @@ def add_layer_norm(x, res, weight, bias, eps):
 
 def vae_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
     """Single-head d=512 attention, q/k/v [B, L, 512] (VAE mid block)."""
-    if _use_hip(q) and q.dtype in _KERNEL_DTYPES and q.shape[-1] == 512:
+    if use_hip(q) and q.dtype in _KERNEL_DTYPES and q.shape[-1] == 512:
         return hip_ext().vae_attention(q, k, v)
     return eager.vae_attention(q, k, v)
 
 
 def geglu(hidden: torch.Tensor) -> torch.Tensor:
-    if _use_hip(hidden):
+    if use_hip(hidden):
         return hip_ext().geglu(hidden)
     return eager.geglu(hidden)

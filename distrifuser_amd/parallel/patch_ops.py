@@ -270,7 +270,7 @@ class PatchGroupNorm(nn.Module):
         comm.wait(self._idx)
         fresh = ops.group_norm_stats(x, self.num_groups)  # [2, N, G, 1, 1, 1]
 
-        if not state.in_warmup and x.is_cuda and not os.environ.get("DFA_FORCE_EAGER") == "1":
+        if not state.in_warmup and ops.use_hip(x):
             # steady state on GPU: ONE fused kernel merges the stale peer
             # moments with the fresh local ones (corrected or substitute),
             # applies the negative-variance guard, and stages fresh into our

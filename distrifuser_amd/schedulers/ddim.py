@@ -34,16 +34,14 @@ class DDIMScheduler(SchedulerBase):
         # this is ONE fused kernel (csrc/scheduler.hip) - the step math runs
         # outside the captured graphs, so its torch-op launch overhead is
         # otherwise exposed every denoise step.
-        import os
+        from ..ops import hip_ext, use_hip
 
         t = int(timestep)
         prev_t = t - self.num_train_timesteps // self.num_inference_steps
         acp = self.alphas_cumprod
         alpha_t = float(acp[t])
         alpha_prev = float(acp[prev_t] if prev_t >= 0 else acp[0])
-        if noise.is_cuda and os.environ.get("DFA_FORCE_EAGER", "0") != "1":
-            from ..ops.dispatch import hip_ext
-
+        if use_hip(noise):
             # x' = sqrt(a_p) * (x - sqrt(1-a_t) eps)/sqrt(a_t) + sqrt(1-a_p) eps
             #    = ca * x + cb * eps
             ca = (alpha_prev / alpha_t) ** 0.5

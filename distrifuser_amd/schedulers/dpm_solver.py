@@ -79,14 +79,12 @@ class DPMSolverMultistepScheduler(SchedulerBase):
         with C = a_p*(exp(-h)-1), C' = C*(1 + 0.5/r0) (order 2) or C (order 1):
             ca = s_p/s_t - C'/a_t,  cb = C'*s_t/a_t,  cc = 0.5*C/r0.
         """
-        import os
+        from ..ops import hip_ext, use_hip
 
-        if not (noise.is_cuda and os.environ.get("DFA_FORCE_EAGER", "0") != "1"):
+        if not use_hip(noise):
             nu, nc = noise.float().chunk(2)
             eps = nu + guidance_scale * (nc - nu)
             return self.step(eps, timestep, sample)
-
-        from ..ops.dispatch import hip_ext
 
         t = int(timestep)
         t_prev = self._prev_timestep(t)

@@ -57,11 +57,9 @@ class EulerDiscreteScheduler(SchedulerBase):
                     guidance_scale: float) -> torch.Tensor:
         # CFG combine + Euler update in ONE fused kernel on GPU (the update is
         # affine in (x, eps): ca = 1, cb = sigma_next - sigma)
-        import os
+        from ..ops import hip_ext, use_hip
 
-        if noise.is_cuda and os.environ.get("DFA_FORCE_EAGER", "0") != "1":
-            from ..ops.dispatch import hip_ext
-
+        if use_hip(noise):
             cb = float(self.sigmas[self._step_index + 1] - self.sigmas[self._step_index])
             self._step_index += 1
             return hip_ext().cfg_affine_step(noise, sample, guidance_scale, 1.0, cb)
