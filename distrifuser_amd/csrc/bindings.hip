@@ -40,9 +40,14 @@ at::Tensor b16_param(const at::Tensor& t, const at::Tensor& ref, const char* op,
 
 // fp32 [2, ngt] sum and sum of squares of x's ngt groups of group_len elements
 at::Tensor gn_partial_stats(const at::Tensor& x, int64_t group_len, int ngt) {
-    auto partial = at::zeros({2, (long)ngt}, x.options().dtype(at::kFloat));
-    launch_gn_stats_partial(x.data_ptr(), partial.data_ptr<float>(), group_len, ngt,
-                            dtype_of(x), cur_stream());
+    const auto f32 = x.options().dtype(at::kFloat);
+    auto partial = at::empty({2, (long)ngt}, f32);
+    const int chunks = gn_stats_chunks(group_len, ngt, dtype_of(x));
+    at::Tensor ws;  // per-chunk sums, added in a fixed order (no atomics)
+    if (chunks > 1) ws = at::empty({2, (long)ngt, (long)chunks}, f32);
+    launch_gn_stats_partial(x.data_ptr(), chunks > 1 ? ws.data_ptr<float>() : nullptr,
+                            partial.data_ptr<float>(), group_len, ngt, dtype_of(x),
+                            cur_stream());
     return partial;
 }
 
@@ -195,6 +200,74 @@ at::Tensor cfg_affine_step(const at::Tensor& noise, const at::Tensor& x, double 
         n.data_ptr(),
         reinterpret_cast<const char*>(n.data_ptr()) + total * n.element_size(), xc.data_ptr(),
         out.data_ptr(), (float)g, (float)ca, (float)cb, total, dtype_of(xc), cur_stream());
+    return out;
+}
+
+// The inputs of a masked (inpaint) step: x [1,C,h,w] and noise [2,C,h,w] (a
+// CFG pair) or [1,C,h,w] (no guidance), one dtype; init and init_noise fp32
+// [1,C,h,w], mask fp32 with h*w elements. The contiguous copies live as long
+// as the struct; nc is null without a CFG pair.
+struct MaskedStepArgs {
+    at::Tensor n, x, init, init_noise, mask;
+    const void* nc;
+    MaskBlend blend;
+};
+MaskedStepArgs masked_step_args(const char* op, const at::Tensor& noise, const at::Tensor& x,
+                                const at::Tensor& init, const at::Tensor& init_noise,
+                                const at::Tensor& mask, double sa, double sb) {
+    TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.size(0) == 1, op, ": x must be CUDA [1,C,h,w]");
+    TORCH_CHECK(noise.is_cuda() && noise.scalar_type() == x.scalar_type() &&
+                    (noise.numel() == x.numel() || noise.numel() == 2 * x.numel()),
+                op, ": noise must be [2,C,h,w] or [1,C,h,w] in x's dtype");
+    const int64_t hw = x.size(2) * x.size(3);
+    auto f32_on_gpu = [&](const at::Tensor& t, int64_t numel, const char* name) {
+        TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.numel() == numel, op, ": ",
+                    name, " must be CUDA fp32 with ", numel, " elements");
+        return t.contiguous();
+    };
+    MaskedStepArgs a{noise.contiguous(), x.contiguous(), f32_on_gpu(init, x.numel(), "init"),
+                     f32_on_gpu(init_noise, x.numel(), "init_noise"),
+                     f32_on_gpu(mask, hw, "mask"), nullptr, {}};
+    if (noise.numel() == 2 * x.numel())
+        a.nc = reinterpret_cast<const char*>(a.n.data_ptr()) + x.numel() * a.n.element_size();
+    a.blend = {a.init.data_ptr<float>(), a.init_noise.data_ptr<float>(),
+               a.mask.data_ptr<float>(), (float)sa, (float)sb, hw};
+    return a;
+}
+
+// cfg_affine_step (or the plain affine step when noise has batch 1), then
+// out = m*x' + (1 - m)*(sa*init + sb*init_noise), in one launch
+at::Tensor masked_affine_step(const at::Tensor& noise, const at::Tensor& x,
+                              const at::Tensor& init, const at::Tensor& init_noise,
+                              const at::Tensor& mask, double g, double ca, double cb, double sa,
+                              double sb) {
+    auto a = masked_step_args("masked_affine_step", noise, x, init, init_noise, mask, sa, sb);
+    auto out = at::empty_like(a.x);
+    launch_cfg_affine_step(a.n.data_ptr(), a.nc, a.x.data_ptr(), out.data_ptr(), (float)g,
+                           (float)ca, (float)cb, a.x.numel(), dtype_of(a.x), cur_stream(),
+                           &a.blend);
+    return out;
+}
+
+// [copies, 9, h, w] = [latents / scale (4), mask (1), masked-image latents (4)]
+at::Tensor inpaint_unet_input(const at::Tensor& latents, const at::Tensor& mask,
+                              const at::Tensor& masked, double scale, int64_t copies) {
+    TORCH_CHECK(latents.is_cuda() && latents.dim() == 4 && latents.size(0) == 1 &&
+                    latents.size(1) == 4,
+                "inpaint_unet_input: latents must be CUDA [1,4,h,w]");
+    const int64_t h = latents.size(2), w = latents.size(3);
+    TORCH_CHECK(mask.is_cuda() && mask.scalar_type() == latents.scalar_type() &&
+                    mask.numel() == h * w,
+                "inpaint_unet_input: mask must be [1,1,h,w] in the latents' dtype");
+    TORCH_CHECK(masked.is_cuda() && masked.scalar_type() == latents.scalar_type() &&
+                    masked.numel() == 4 * h * w,
+                "inpaint_unet_input: masked latents must be [1,4,h,w] in the latents' dtype");
+    TORCH_CHECK(copies == 1 || copies == 2, "inpaint_unet_input: copies must be 1 or 2");
+    TORCH_CHECK(scale > 0, "inpaint_unet_input: scale must be positive");
+    auto l = latents.contiguous(), m = mask.contiguous(), ml = masked.contiguous();
+    auto out = at::empty({copies, 9, h, w}, l.options());
+    launch_inpaint_unet_input(l.data_ptr(), m.data_ptr(), ml.data_ptr(), out.data_ptr(),
+                              (float)scale, h * w, (int)copies, dtype_of(l), cur_stream());
     return out;
 }
 
@@ -471,6 +544,28 @@ at::Tensor conv3x3(const at::Tensor& x, const at::Tensor& wp,
     return o;
 }
 
+// n / nc: the contiguous noise and its cond half (null: no CFG pair, masked
+// only); xc contiguous. -> (prev, x0 fp32)
+std::vector<at::Tensor> dpm_step(const at::Tensor& n, const void* nc, const at::Tensor& xc,
+                                 const c10::optional<at::Tensor>& x0_prev, double g, double ca,
+                                 double cb, double cc, double cx, double ce,
+                                 const MaskBlend* blend) {
+    const void* pp = nullptr;
+    at::Tensor p;
+    if (x0_prev.has_value()) {
+        p = x0_prev->contiguous();
+        TORCH_CHECK(p.is_cuda() && p.numel() == xc.numel() && p.scalar_type() == at::kFloat,
+                    "x0_prev must be the fp32 state from the previous cfg_dpm_step");
+        pp = p.data_ptr();
+    }
+    auto out = at::empty_like(xc);
+    auto x0 = at::empty_like(xc, xc.options().dtype(at::kFloat));
+    launch_cfg_dpm_step(n.data_ptr(), nc, xc.data_ptr(), pp, out.data_ptr(), x0.data_ptr(),
+                        (float)g, (float)ca, (float)cb, (float)cc, (float)cx, (float)ce,
+                        xc.numel(), dtype_of(xc), cur_stream(), blend);
+    return {out, x0};
+}
+
 std::vector<at::Tensor> cfg_dpm_step(const at::Tensor& noise, const at::Tensor& x,
                                      const c10::optional<at::Tensor>& x0_prev, double g,
                                      double ca, double cb, double cc, double cx, double ce) {
@@ -478,23 +573,19 @@ std::vector<at::Tensor> cfg_dpm_step(const at::Tensor& noise, const at::Tensor& 
     auto n = noise.contiguous();
     auto xc = x.contiguous();
     TORCH_CHECK(xc.numel() * 2 == n.numel());
-    const void* pp = nullptr;
-    at::Tensor p;
-    if (x0_prev.has_value()) {
-        p = x0_prev->contiguous();
-        TORCH_CHECK(p.numel() == xc.numel() && p.scalar_type() == at::kFloat,
-                    "x0_prev must be the fp32 state from the previous cfg_dpm_step");
-        pp = p.data_ptr();
-    }
-    auto out = at::empty_like(xc);
-    auto x0 = at::empty_like(xc, xc.options().dtype(at::kFloat));
-    const int64_t total = xc.numel();
-    launch_cfg_dpm_step(n.data_ptr(),
-                        reinterpret_cast<const char*>(n.data_ptr()) + total * n.element_size(),
-                        xc.data_ptr(), pp, out.data_ptr(), x0.data_ptr(), (float)g, (float)ca,
-                        (float)cb, (float)cc, (float)cx, (float)ce, total, dtype_of(xc),
-                        cur_stream());
-    return {out, x0};
+    const void* nc =
+        reinterpret_cast<const char*>(n.data_ptr()) + xc.numel() * n.element_size();
+    return dpm_step(n, nc, xc, x0_prev, g, ca, cb, cc, cx, ce, nullptr);
+}
+
+// cfg_dpm_step with the inpaint blend on prev; x0 is the unmasked step's
+std::vector<at::Tensor> masked_dpm_step(const at::Tensor& noise, const at::Tensor& x,
+                                        const c10::optional<at::Tensor>& x0_prev,
+                                        const at::Tensor& init, const at::Tensor& init_noise,
+                                        const at::Tensor& mask, double g, double ca, double cb,
+                                        double cc, double cx, double ce, double sa, double sb) {
+    auto a = masked_step_args("masked_dpm_step", noise, x, init, init_noise, mask, sa, sb);
+    return dpm_step(a.n, a.nc, a.x, x0_prev, g, ca, cb, cc, cx, ce, &a.blend);
 }
 
 at::Tensor layer_norm(const at::Tensor& x_, const at::Tensor& w_, const at::Tensor& b_,
@@ -601,6 +692,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("o_parts"), pybind11::arg("lse_parts"), pybind11::arg("out_bf16") = true,
           pybind11::arg("out_dtype") = pybind11::none());
     m.def("cfg_dpm_step", &cfg_dpm_step, "fused CFG + DPM-Solver++(2M) update -> (prev, x0)");
+    m.def("masked_affine_step", &masked_affine_step,
+          "inpaint: (CFG +) affine scheduler update blended with the re-noised init latents");
+    m.def("masked_dpm_step", &masked_dpm_step,
+          "inpaint: (CFG +) DPM-Solver++(2M) update, prev blended -> (prev, x0)");
+    m.def("inpaint_unet_input", &inpaint_unet_input,
+          "inpaint U-Net input [copies,9,h,w] = [latents / scale, mask, masked-image latents]");
     m.def("layer_norm", &layer_norm, "bf16/fp16 fused LayerNorm");
     m.def("add_layer_norm", &add_layer_norm, "bf16/fp16 fused residual-add + LayerNorm -> (sum, y)");
     m.def("vae_attention", &vae_attention, "bf16/fp16 single-head d=512 VAE mid attention");

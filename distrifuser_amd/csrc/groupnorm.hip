@@ -4,9 +4,12 @@
 // HBM-bandwidth-bound on MI355X (8 TB/s), so everything is vectorized to
 // 16 B/lane and SiLU is fused into the normalization epilogue (every GN in an
 // SD ResBlock is followed by SiLU — fusing halves the traffic of a separate
-// activation pass). Stats use a grid-strided partial-reduction kernel with
-// one atomicAdd pair per block (device-scope atomics are XCD-safe, guide §6
-// G12); each (sample, group) slab is contiguous in NCHW.
+// activation pass). Stats use a grid-strided partial-reduction kernel: every
+// block stores the sums of its chunk, and a second small kernel adds a group's
+// chunks in a fixed order, so the moments are the same bits on every run and
+// on every rank (atomic adds would land in scheduling order; one last-bit
+// difference in the VAE encoder's moments is enough to move the img2img and
+// inpaint init latents). Each (sample, group) slab is contiguous in NCHW.
 
 #include "boundary_plan.h"
 #include "dispatch.h"
@@ -45,10 +48,24 @@ __global__ void gn_stats_partial_kernel(const T* __restrict__ x, float* __restri
     }
     __shared__ float lds[2 * 16];
     block_reduce_sum2(s, ss, lds);
+    // partial: [2][ngt][chunks]
     if (threadIdx.x == 0) {
-        atomicAdd(&partial[ng], s);
-        atomicAdd(&partial[ngt + ng], ss);
+        partial[(int64_t)ng * chunks + chunk] = s;
+        partial[((int64_t)ngt + ng) * chunks + chunk] = ss;
     }
+}
+
+// out[e] = sum over the chunks of ws[e][:], e in [0, 2*ngt): one wave per
+// entry, lane-strided partial sums and a butterfly, the same order every time
+__global__ void gn_reduce_chunks_kernel(const float* __restrict__ ws, float* __restrict__ out,
+                                        int chunks, int entries) {
+    const int e = blockIdx.x * (blockDim.x / WAVE_SIZE) + threadIdx.x / WAVE_SIZE;
+    if (e >= entries) return;
+    const int lane = threadIdx.x % WAVE_SIZE;
+    float v = 0.f;
+    for (int c = lane; c < chunks; c += WAVE_SIZE) v += ws[(int64_t)e * chunks + c];
+    v = wave_all_reduce_sum(v);
+    if (lane == 0) out[e] = v;
 }
 
 template <typename T>
@@ -400,21 +417,35 @@ void launch_gn_merge_stats(void* buffer, int64_t row_stride, int64_t slot_off, i
     });
 }
 
-void launch_gn_stats_partial(const void* x, float* partial, int64_t group_len, int ngt, int dtype,
-                             hipStream_t stream) {
+int gn_stats_chunks(int64_t group_len, int ngt, int dtype) {
+    int chunks = 1;
+    dispatch_dtype(dtype, [&]<typename T>(std::type_identity<T>) {
+        const int V = group_len % VecN<T>::value == 0 ? VecN<T>::value : 1;
+        // size chunks so the chip is filled: >= 2048 blocks total
+        chunks = (int)std::max<int64_t>(1, (2048 + ngt - 1) / ngt);
+        // but never more chunks than work
+        int64_t nvec = std::max<int64_t>(group_len / V, 1);
+        chunks = (int)std::min<int64_t>(chunks, (nvec + 255) / 256);
+        chunks = std::max(chunks, 1);
+    });
+    return chunks;
+}
+
+void launch_gn_stats_partial(const void* x, float* ws, float* partial, int64_t group_len, int ngt,
+                             int dtype, hipStream_t stream) {
+    const int chunks = gn_stats_chunks(group_len, ngt, dtype);
     dispatch_dtype(dtype, [&]<typename T>(std::type_identity<T>) {
         dispatch_bool(group_len % VecN<T>::value == 0, [&]<bool VEC>(std::bool_constant<VEC>) {
-            // size chunks so the chip is filled: >= 2048 blocks total
-            constexpr int V = VEC ? VecN<T>::value : 1;
-            int chunks = (int)std::max<int64_t>(1, (2048 + ngt - 1) / ngt);
-            // but never more chunks than work
-            int64_t nvec = std::max<int64_t>(group_len / V, 1);
-            chunks = (int)std::min<int64_t>(chunks, (nvec + 255) / 256);
-            chunks = std::max(chunks, 1);
+            // one chunk: the block's sums are the group's, straight into partial
             gn_stats_partial_kernel<T, VEC><<<dim3(ngt * chunks), 256, 0, stream>>>(
-                (const T*)x, partial, group_len, chunks, ngt);
+                (const T*)x, chunks == 1 ? partial : ws, group_len, chunks, ngt);
         });
     });
+    if (chunks > 1) {
+        const int waves = 4, entries = 2 * ngt;
+        gn_reduce_chunks_kernel<<<(entries + waves - 1) / waves, waves * WAVE_SIZE, 0, stream>>>(
+            ws, partial, chunks, entries);
+    }
 }
 
 void launch_gn_finalize(const float* partial, void* out, float inv_count, int ngt, int dtype,

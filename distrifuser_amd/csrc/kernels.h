@@ -7,8 +7,12 @@
 enum DfaDtype : int { DFA_BF16 = 0, DFA_F16 = 1, DFA_F32 = 2 };
 
 // ---- GroupNorm family ------------------------------------------------------
-// partial: fp32 [2, N*G] zero-initialized; accumulates sum and sumsq.
-void launch_gn_stats_partial(const void* x, float* partial, int64_t group_len,
+// partial: fp32 [2, N*G], receives sum and sumsq (no initialisation needed).
+// A group is summed by gn_stats_chunks() blocks; with more than one, they
+// store into ws, fp32 [2, N*G, chunks], and a second launch adds the chunks
+// in a fixed order: the same bits on every run. ws is not read with one chunk.
+int gn_stats_chunks(int64_t group_len, int n_groups_total, int dtype);
+void launch_gn_stats_partial(const void* x, float* ws, float* partial, int64_t group_len,
                              int n_groups_total, int dtype, hipStream_t stream);
 // out: [2, N*G] in `dtype`; mean = partial/count.
 void launch_gn_finalize(const float* partial, void* out, float inv_count,
@@ -54,10 +58,32 @@ void launch_gn_merge_stats(void* buffer, int64_t row_stride, int64_t slot_off,
 void launch_geglu(const void* in, void* out, int64_t rows, int64_t inner, int dtype,
                   hipStream_t stream);
 
+// ---- inpaint blend of a masked scheduler step -------------------------------
+// known = sa*init + sb*init_noise; out = m*x' + (1 - m)*known, in fp32, rounded
+// once. init and init_noise: fp32 [C*hw], one value per latent element; mask:
+// fp32 [hw], element i reads mask[i % hw] (broadcast over channels).
+struct MaskBlend {
+    const float* init;
+    const float* init_noise;
+    const float* mask;
+    float sa, sb;
+    int64_t hw;
+};
+
 // ---- fused CFG + scheduler step (affine: out = ca*x + cb*eps) ---------------
+// blend != null: the masked step, total = C*hw; noise_c may then be null (no
+// CFG pair: eps = noise_u, g is not read). Its 16-byte path needs hw a
+// multiple of the vector width and 16-byte aligned pointers.
 void launch_cfg_affine_step(const void* noise_u, const void* noise_c, const void* x, void* out,
                             float g, float ca, float cb, int64_t total, int dtype,
-                            hipStream_t stream);
+                            hipStream_t stream, const MaskBlend* blend = nullptr);
+
+// ---- inpaint U-Net input assembly --------------------------------------------
+// out [copies, 9, hw]: channels 0..3 = latents [4, hw] / scale, channel 4 =
+// mask [hw], channels 5..8 = masked [4, hw] (4..8 copied bit for bit).
+void launch_inpaint_unet_input(const void* latents, const void* mask, const void* masked,
+                               void* out, float scale, int64_t hw, int copies, int dtype,
+                               hipStream_t stream);
 
 // ---- Implicit-GEMM 3x3 conv (bf16 or fp16, NCHW, stride 1/2, pad 1) -----------------
 // x: interior [B][Cin][H][W] (row-contiguous; x_sc = channel stride).
@@ -92,9 +118,12 @@ void launch_conv3x3(const Conv3x3Params& p, int stride, int dtype, hipStream_t s
 
 // ---- fused CFG + DPM-Solver++(2M) step --------------------------------------
 // out = ca*x + cb*eps + cc*x0_prev (x0_prev may be null); x0_out = cx*x + ce*eps
+// blend != null: out is blended as in the masked affine step (nc may be null);
+// x0_out is not.
 void launch_cfg_dpm_step(const void* nu, const void* nc, const void* x, const void* x0_prev,
                          void* out, void* x0_out, float g, float ca, float cb, float cc,
-                         float cx, float ce, int64_t total, int dtype, hipStream_t stream);
+                         float cx, float ce, int64_t total, int dtype, hipStream_t stream,
+                         const MaskBlend* blend = nullptr);
 
 // ---- fused (residual +) LayerNorm (bf16 or fp16, C <= 2048, C % 8 == 0) -------------
 // y = LN(x [+ res]); when res != null and sum_out != null, x+res is also

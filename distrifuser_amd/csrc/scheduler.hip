@@ -9,16 +9,65 @@
 // DDIM:  ca = sqrt(a_prev/a_t), cb = sqrt(1-a_prev) - ca * sqrt(1-a_t)
 // Euler: ca = 1,                cb = sigma_next - sigma
 // Reference numerics: schedulers/{ddim,euler}.py + pipelines._denoise.
+//
+// Inpainting (the MASKED axis of both step kernels) blends the step's result
+// with the known region, the init latents re-noised to the next timestep:
+//
+//   known = sa * init + sb * init_noise
+//   out   = m * x' + (1 - m) * known      (fp32, rounded once to T)
+//
+// In this form m == 1 returns x' and m == 0 returns known, and sa = 1, sb = 0
+// makes known == init: exactly for finite inputs, up to the sign of a zero (a
+// -0.0 comes out as +0.0, since the term that vanishes is +0), while a
+// non-finite value on the vanishing side gives NaN (0 * inf). init, init_noise
+// (one fp32 value per latent element) and m (one per pixel, shared by the
+// channels) are read-only. A masked step also runs without a CFG pair:
+// noise_c null means eps = nu.
 
 #include "dispatch.h"
 
 namespace {
 
-template <typename T, bool VEC>
+// V consecutive fp32 values, 16 bytes at a time (p 16-byte aligned)
+template <int V>
+__device__ __forceinline__ void load_f32(float (&dst)[V], const float* __restrict__ p) {
+#pragma unroll
+    for (int q = 0; q < V / 4; ++q)
+        *reinterpret_cast<float4*>(&dst[q * 4]) = *reinterpret_cast<const float4*>(p + q * 4);
+}
+
+// eps and x' of the masked kernels, with every rounding written out: m == 1
+// must return the unmasked step bit for bit, so they round where the unmasked
+// instantiation of the same (T, VEC) rounds (tests/test_inpaint_ops_gpu.py
+// holds the two together). eps is one fma everywhere; x' is
+// fma(ca, x, round(cb*eps)) when FUSED (the affine kernel's 16-byte path, which
+// the unmasked launcher takes for every [1,4,h,w] fp32 tensor, and the 16-bit
+// kernels) and round(ca*x) + round(cb*eps) when not (the fp32 DPM kernel, and
+// x0 of every DPM kernel).
+__device__ __forceinline__ float cfg_eps(float nu, float nc, float g) {
+    return __builtin_fmaf(g, nc - nu, nu);
+}
+template <bool FUSED>
+__device__ __forceinline__ float affine_xp(float ca, float x, float cb, float eps) {
+#pragma clang fp contract(off)
+    const float t = cb * eps;
+    if constexpr (FUSED) return __builtin_fmaf(ca, x, t);
+    const float s = ca * x;
+    return s + t;
+}
+
+__device__ __forceinline__ float mask_blend(float xp, float m, float init, float init_noise,
+                                            float sa, float sb) {
+    const float known = sa * init + sb * init_noise;
+    return m * xp + (1.f - m) * known;
+}
+
+// VEC && MASKED: hw % V == 0, so a vector never straddles a plane
+template <typename T, bool VEC, bool MASKED>
 __global__ void cfg_affine_step_kernel(const T* __restrict__ noise_u,
                                        const T* __restrict__ noise_c, const T* __restrict__ x,
                                        T* __restrict__ out, float g, float ca, float cb,
-                                       int64_t total) {
+                                       int64_t total, MaskBlend bl) {
     constexpr int V = VEC ? VecN<T>::value : 1;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t vid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; vid * V < total;
@@ -26,20 +75,41 @@ __global__ void cfg_affine_step_kernel(const T* __restrict__ noise_u,
         const int64_t i = vid * V;
         if (VEC) {
             uint4 ur = *reinterpret_cast<const uint4*>(noise_u + i);
-            uint4 cr = *reinterpret_cast<const uint4*>(noise_c + i);
+            uint4 cr = ur;
+            if (!MASKED || noise_c) cr = *reinterpret_cast<const uint4*>(noise_c + i);
             uint4 xr = *reinterpret_cast<const uint4*>(x + i);
             const T* u = reinterpret_cast<const T*>(&ur);
             const T* c = reinterpret_cast<const T*>(&cr);
             const T* xi = reinterpret_cast<const T*>(&xr);
             uint4 orw;
             T* o = reinterpret_cast<T*>(&orw);
+            if constexpr (MASKED) {
+                alignas(16) float iv[V], nv[V], mv[V];
+                load_f32<V>(iv, bl.init + i);
+                load_f32<V>(nv, bl.init_noise + i);
+                load_f32<V>(mv, bl.mask + i % bl.hw);
 #pragma unroll
-            for (int j = 0; j < V; ++j) {
-                const float nu = to_f32(u[j]);
-                const float eps = nu + g * (to_f32(c[j]) - nu);
-                o[j] = from_f32<T>(ca * to_f32(xi[j]) + cb * eps);
+                for (int j = 0; j < V; ++j) {
+                    const float nu = to_f32(u[j]);
+                    const float eps = noise_c ? cfg_eps(nu, to_f32(c[j]), g) : nu;
+                    const float xp = affine_xp<true>(ca, to_f32(xi[j]), cb, eps);
+                    o[j] = from_f32<T>(mask_blend(xp, mv[j], iv[j], nv[j], bl.sa, bl.sb));
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    const float nu = to_f32(u[j]);
+                    const float eps = nu + g * (to_f32(c[j]) - nu);
+                    o[j] = from_f32<T>(ca * to_f32(xi[j]) + cb * eps);
+                }
             }
             *reinterpret_cast<uint4*>(out + i) = orw;
+        } else if constexpr (MASKED) {
+            const float nu = to_f32(noise_u[i]);
+            const float eps = noise_c ? cfg_eps(nu, to_f32(noise_c[i]), g) : nu;
+            const float xp = affine_xp<true>(ca, to_f32(x[i]), cb, eps);
+            out[i] = from_f32<T>(mask_blend(xp, bl.mask[i % bl.hw], bl.init[i], bl.init_noise[i],
+                                            bl.sa, bl.sb));
         } else {
             const float nu = to_f32(noise_u[i]);
             const float eps = nu + g * (to_f32(noise_c[i]) - nu);
@@ -48,17 +118,28 @@ __global__ void cfg_affine_step_kernel(const T* __restrict__ noise_u,
     }
 }
 
+bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+
 }  // namespace
 
 void launch_cfg_affine_step(const void* noise_u, const void* noise_c, const void* x, void* out,
                             float g, float ca, float cb, int64_t total, int dtype,
-                            hipStream_t stream) {
+                            hipStream_t stream, const MaskBlend* blend) {
     const int block = 256;
     dispatch_dtype(dtype, [&]<typename T>(std::type_identity<T>) {
-        dispatch_bool(total % VecN<T>::value == 0, [&]<bool VEC>(std::bool_constant<VEC>) {
-            const int grid = grid_for(total / (VEC ? VecN<T>::value : 1), block);
-            cfg_affine_step_kernel<T, VEC><<<grid, block, 0, stream>>>(
-                (const T*)noise_u, (const T*)noise_c, (const T*)x, (T*)out, g, ca, cb, total);
+        dispatch_bool(blend != nullptr, [&]<bool MASKED>(std::bool_constant<MASKED>) {
+            bool vec = total % VecN<T>::value == 0;
+            if constexpr (MASKED)
+                vec = blend->hw % VecN<T>::value == 0 && aligned16(noise_u) &&
+                      aligned16(noise_c) && aligned16(x) && aligned16(out) &&
+                      aligned16(blend->init) && aligned16(blend->init_noise) &&
+                      aligned16(blend->mask);
+            dispatch_bool(vec, [&]<bool VEC>(std::bool_constant<VEC>) {
+                const int grid = grid_for(total / (VEC ? VecN<T>::value : 1), block);
+                cfg_affine_step_kernel<T, VEC, MASKED><<<grid, block, 0, stream>>>(
+                    (const T*)noise_u, (const T*)noise_c, (const T*)x, (T*)out, g, ca, cb, total,
+                    MASKED ? *blend : MaskBlend{});
+            });
         });
     });
 }
@@ -69,21 +150,31 @@ namespace {
 // x0 = cx*x + ce*eps for the next step (x0_prev null on the first step).
 // x0 state kept in fp32: it reaches ~1/alpha_t * x magnitudes early in the
 // trajectory, where bf16 granularity visibly perturbs the 2M correction.
-template <typename T>
+// MASKED blends out alone: x0_out is the unmasked kernel's, bit for bit.
+template <typename T, bool MASKED>
 __global__ void cfg_dpm_step_kernel(const T* __restrict__ noise_u, const T* __restrict__ noise_c,
                                     const T* __restrict__ x, const float* __restrict__ x0_prev,
                                     T* __restrict__ out, float* __restrict__ x0_out, float g,
                                     float ca, float cb, float cc, float cx, float ce,
-                                    int64_t total) {
+                                    int64_t total, MaskBlend bl) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
         const float nu = to_f32(noise_u[i]);
-        const float eps = nu + g * (to_f32(noise_c[i]) - nu);
         const float xf = to_f32(x[i]);
-        float prev = ca * xf + cb * eps;
-        if (x0_prev) prev += cc * x0_prev[i];
-        out[i] = from_f32<T>(prev);
-        x0_out[i] = cx * xf + ce * eps;
+        if constexpr (MASKED) {
+            const float eps = noise_c ? cfg_eps(nu, to_f32(noise_c[i]), g) : nu;
+            float prev = affine_xp<sizeof(T) == 2>(ca, xf, cb, eps);
+            if (x0_prev) prev = __builtin_fmaf(cc, x0_prev[i], prev);
+            out[i] = from_f32<T>(mask_blend(prev, bl.mask[i % bl.hw], bl.init[i],
+                                            bl.init_noise[i], bl.sa, bl.sb));
+            x0_out[i] = affine_xp<false>(cx, xf, ce, eps);
+        } else {
+            const float eps = nu + g * (to_f32(noise_c[i]) - nu);
+            float prev = ca * xf + cb * eps;
+            if (x0_prev) prev += cc * x0_prev[i];
+            out[i] = from_f32<T>(prev);
+            x0_out[i] = cx * xf + ce * eps;
+        }
     }
 }
 
@@ -91,12 +182,67 @@ __global__ void cfg_dpm_step_kernel(const T* __restrict__ noise_u, const T* __re
 
 void launch_cfg_dpm_step(const void* nu, const void* nc, const void* x, const void* x0_prev,
                          void* out, void* x0_out, float g, float ca, float cb, float cc,
-                         float cx, float ce, int64_t total, int dtype, hipStream_t stream) {
+                         float cx, float ce, int64_t total, int dtype, hipStream_t stream,
+                         const MaskBlend* blend) {
     const int block = 256;
     const int grid = grid_for(total, block);
     dispatch_dtype(dtype, [&]<typename T>(std::type_identity<T>) {
-        cfg_dpm_step_kernel<T><<<grid, block, 0, stream>>>(
-            (const T*)nu, (const T*)nc, (const T*)x, (const float*)x0_prev, (T*)out,
-            (float*)x0_out, g, ca, cb, cc, cx, ce, total);
+        dispatch_bool(blend != nullptr, [&]<bool MASKED>(std::bool_constant<MASKED>) {
+            cfg_dpm_step_kernel<T, MASKED><<<grid, block, 0, stream>>>(
+                (const T*)nu, (const T*)nc, (const T*)x, (const float*)x0_prev, (T*)out,
+                (float*)x0_out, g, ca, cb, cc, cx, ce, total, MASKED ? *blend : MaskBlend{});
+        });
+    });
+}
+
+namespace {
+
+// out [copies, 9, hw]: channels 0..3 latents / scale (rounded once), channel 4
+// the mask and 5..8 the masked-image latents, both copied bit for bit; every
+// copy is the same. VEC: hw % V == 0, a vector stays inside one channel plane.
+template <typename T, bool VEC>
+__global__ void inpaint_unet_input_kernel(const T* __restrict__ latents,
+                                          const T* __restrict__ mask,
+                                          const T* __restrict__ masked, T* __restrict__ out,
+                                          float scale, int64_t hw, int copies) {
+    constexpr int V = VEC ? VecN<T>::value : 1;
+    const int64_t per_copy = 9 * hw;
+    const int64_t total = per_copy * copies;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t vid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; vid * V < total;
+         vid += stride) {
+        const int64_t i = vid * V;
+        const int64_t r = i % per_copy;  // offset inside one copy
+        const int c = (int)(r / hw);
+        const T* src = c < 4 ? latents + r : (c == 4 ? mask + (r - 4 * hw) : masked + (r - 5 * hw));
+        if (VEC) {
+            uint4 raw = *reinterpret_cast<const uint4*>(src);
+            if (c < 4) {
+                T* e = reinterpret_cast<T*>(&raw);
+#pragma unroll
+                for (int j = 0; j < V; ++j) e[j] = from_f32<T>(to_f32(e[j]) / scale);
+            }
+            *reinterpret_cast<uint4*>(out + i) = raw;
+        } else {
+            out[i] = c < 4 ? from_f32<T>(to_f32(*src) / scale) : *src;
+        }
+    }
+}
+
+}  // namespace
+
+void launch_inpaint_unet_input(const void* latents, const void* mask, const void* masked,
+                               void* out, float scale, int64_t hw, int copies, int dtype,
+                               hipStream_t stream) {
+    const int block = 256;
+    const int64_t total = 9 * hw * copies;
+    dispatch_dtype(dtype, [&]<typename T>(std::type_identity<T>) {
+        const bool vec = hw % VecN<T>::value == 0 && aligned16(latents) && aligned16(mask) &&
+                         aligned16(masked) && aligned16(out);
+        dispatch_bool(vec, [&]<bool VEC>(std::bool_constant<VEC>) {
+            const int grid = grid_for(total / (VEC ? VecN<T>::value : 1), block);
+            inpaint_unet_input_kernel<T, VEC><<<grid, block, 0, stream>>>(
+                (const T*)latents, (const T*)mask, (const T*)masked, (T*)out, scale, hw, copies);
+        });
     });
 }

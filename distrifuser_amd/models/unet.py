@@ -10,7 +10,7 @@ checkpoints load 1:1 (models/weights.py).
 
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 
 import torch
 from torch import nn
@@ -68,6 +68,12 @@ SD15_UNET = UNetConfig(
     addition_embed_type=None,
     sample_size=64,
 )
+
+# 9-channel inpaint checkpoints (stable-diffusion-inpainting,
+# stable-diffusion-xl-1.0-inpainting-0.1): conv_in takes
+# [latents (4), mask (1), masked-image latents (4)]
+SDXL_INPAINT_UNET = replace(SDXL_UNET, in_channels=9)
+SD15_INPAINT_UNET = replace(SD15_UNET, in_channels=9)
 
 # stabilityai/stable-diffusion-2-1 unet/config.json shapes
 SD21_UNET = UNetConfig(

@@ -19,7 +19,10 @@ from .dispatch import (
     group_norm_stats,
     hip_ext,
     hip_ext_available,
+    inpaint_unet_input,
     layer_norm,
+    masked_affine_step,
+    masked_dpm_step,
     merge_attention,
     tokens_add_nchw,
     use_hip,
@@ -42,6 +45,9 @@ __all__ = [
     "group_norm_stats",
     "hip_ext",
     "hip_ext_available",
+    "inpaint_unet_input",
+    "masked_affine_step",
+    "masked_dpm_step",
     "merge_attention",
     "pack_conv3x3_weight",
     "tokens_add_nchw",

@@ -287,6 +287,46 @@ def tokens_add_nchw(y: torch.Tensor, residual: torch.Tensor) -> torch.Tensor:
     return eager.tokens_add_nchw(y, residual)
 
 
+def _f32(t: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
+    return t.to(device=like.device, dtype=torch.float32)
+
+
+def masked_affine_step(noise, x, init, init_noise, mask, g, ca, cb, sa, sb):
+    """Inpaint step of DDIM / Euler in one launch on GPU:
+
+        eps = nu + g*(nc - nu)   (noise [2,C,h,w]; eps = noise for [1,C,h,w])
+        x'  = ca*x + cb*eps
+        out = m*x' + (1 - m)*(sa*init + sb*init_noise)
+
+    x [1,C,h,w] in bf16, fp16 or fp32; init, init_noise fp32 [1,C,h,w]; mask
+    fp32 with h*w elements, shared by the channels."""
+    if use_hip(x) and x.dtype in _BOUNDARY_DTYPES:
+        return hip_ext().masked_affine_step(noise, x, _f32(init, x), _f32(init_noise, x),
+                                            _f32(mask, x), g, ca, cb, sa, sb)
+    return eager.masked_affine_step(noise, x, init, init_noise, mask, g, ca, cb, sa, sb)
+
+
+def masked_dpm_step(noise, x, x0_prev, init, init_noise, mask, g, ca, cb, cc, cx, ce, sa, sb):
+    """Inpaint step of DPM-Solver++(2M): cfg_dpm_step with the blend of
+    masked_affine_step on prev. Returns (prev, x0); x0 (fp32) is not blended."""
+    if use_hip(x) and x.dtype in _BOUNDARY_DTYPES:
+        prev, x0 = hip_ext().masked_dpm_step(noise, x, x0_prev, _f32(init, x),
+                                             _f32(init_noise, x), _f32(mask, x), g, ca, cb, cc,
+                                             cx, ce, sa, sb)
+        return prev, x0
+    return eager.masked_dpm_step(noise, x, x0_prev, init, init_noise, mask, g, ca, cb, cc, cx,
+                                 ce, sa, sb)
+
+
+def inpaint_unet_input(latents, mask, masked_latents, scale=1.0, copies=1):
+    """The 9-channel inpaint U-Net input [copies, 9, h, w] in one launch on
+    GPU: latents [1,4,h,w] / scale, the mask [1,1,h,w] and the masked-image
+    latents [1,4,h,w], all in the latents' dtype; copies is 2 with CFG."""
+    if use_hip(latents) and latents.dtype in _BOUNDARY_DTYPES:
+        return hip_ext().inpaint_unet_input(latents, mask, masked_latents, scale, copies)
+    return eager.inpaint_unet_input(latents, mask, masked_latents, scale, copies)
+
+
 def layer_norm(x, weight, bias, eps):
     if use_hip(x) and x.dtype in _KERNEL_DTYPES and x.shape[-1] % 8 == 0 and x.shape[-1] <= 2048:
         return hip_ext().layer_norm(x, weight, bias, eps)

@@ -171,6 +171,53 @@ def vae_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.Te
     return torch.einsum("bqk,bkc->bqc", probs, v.float()).to(q.dtype)
 
 
+def _cfg_eps(noise: torch.Tensor, x: torch.Tensor, g: float) -> torch.Tensor:
+    """fp32 eps of a step: the CFG combine of a [uncond; cond] pair, or the
+    noise itself when it has x's batch (no guidance, g not read)."""
+    n = noise.float()
+    if n.shape[0] == x.shape[0]:
+        return n
+    nu, nc = n.chunk(2)
+    return nu + g * (nc - nu)
+
+
+def _mask_blend(xp, x, init, init_noise, mask, sa, sb):
+    """out = m*x' + (1 - m)*(sa*init + sb*init_noise) in fp32, rounded once to
+    x's dtype. In this form m == 1 gives x' and m == 0 gives known exactly."""
+    m = mask.float().reshape(1, 1, x.shape[2], x.shape[3])
+    known = sa * init.float() + sb * init_noise.float()
+    return (m * xp + (1.0 - m) * known).to(x.dtype)
+
+
+def masked_affine_step(noise, x, init, init_noise, mask, g, ca, cb, sa, sb):
+    """Inpaint step of the affine schedulers (DDIM, Euler): x' = ca*x + cb*eps
+    blended with the known region. noise [2,C,h,w] (CFG pair) or [1,C,h,w];
+    x [1,C,h,w]; init, init_noise fp32 [1,C,h,w]; mask h*w elements, shared by
+    the channels."""
+    xp = ca * x.float() + cb * _cfg_eps(noise, x, g)
+    return _mask_blend(xp, x, init, init_noise, mask, sa, sb)
+
+
+def masked_dpm_step(noise, x, x0_prev, init, init_noise, mask, g, ca, cb, cc, cx, ce, sa, sb):
+    """Inpaint step of DPM-Solver++(2M): prev = ca*x + cb*eps (+ cc*x0_prev)
+    blended with the known region; x0 = cx*x + ce*eps (fp32) is the unmasked
+    step's. Returns (prev, x0)."""
+    eps = _cfg_eps(noise, x, g)
+    xf = x.float()
+    prev = ca * xf + cb * eps
+    if x0_prev is not None:
+        prev = prev + cc * x0_prev.float()
+    return _mask_blend(prev, x, init, init_noise, mask, sa, sb), cx * xf + ce * eps
+
+
+def inpaint_unet_input(latents, mask, masked_latents, scale=1.0, copies=1):
+    """[copies, 9, h, w]: latents [1,4,h,w] / scale, then the mask [1,1,h,w]
+    and the masked-image latents [1,4,h,w] as they are (the latents' dtype)."""
+    scaled = (latents.float() / scale).to(latents.dtype)
+    one = torch.cat([scaled, mask.reshape(1, 1, *latents.shape[2:]), masked_latents], dim=1)
+    return one.repeat(copies, 1, 1, 1)
+
+
 def conv3x3_halo(
     x: torch.Tensor,
     weight: torch.Tensor,

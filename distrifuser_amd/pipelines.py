@@ -22,8 +22,10 @@ import torch
 from .models.clip import CLIP_VIT_L, OPEN_CLIP_BIG_G, TINY_CLIP, CLIPTextEncoder
 from .models.distri_unet import DistriUNet
 from .models.tokenizer import CLIPBPETokenizer, SimpleTokenizer, load_clip_tokenizer
-from .models.unet import SD15_UNET, SDXL_UNET, TINY_UNET, UNetConfig
+from .models.unet import (SD15_INPAINT_UNET, SD15_UNET, SDXL_INPAINT_UNET, SDXL_UNET, TINY_UNET,
+                          UNetConfig)
 from .models.vae import SD_VAE, SDXL_VAE, TINY_VAE, VAEDecoder, VAEEncoder
+from . import ops
 from .models import weights as weight_io
 from .schedulers import get_scheduler
 from .schedulers.common import img2img_start
@@ -165,9 +167,15 @@ class _DistriPipelineBase:
     def _unet_dtype(self) -> torch.dtype:
         return next(self.unet.parameters()).dtype
 
-    def _prepare_latents(self, batch_size: int, generator) -> torch.Tensor:
+    def _prepare_latents(self, batch_size: int, generator,
+                         channels: int | None = None) -> torch.Tensor:
+        """Initial noise with the VAE's latent channels, or with ``channels``
+        (the U-Net's input width for the static graph inputs: a 9-channel
+        inpaint U-Net takes more than the latents)."""
         cfg = self.distri_config
-        shape = (batch_size, self.unet.config.in_channels, cfg.height // 8, cfg.width // 8)
+        if channels is None:
+            channels = self.vae.config.latent_channels
+        shape = (batch_size, channels, cfg.height // 8, cfg.width // 8)
         if generator is None:
             # Cross-rank determinism: every rank MUST sample identical initial
             # latents (they denoise the same image). Default to a fixed seed.
@@ -257,13 +265,96 @@ class _DistriPipelineBase:
                                            self.scheduler.timesteps[t_start])
         return latents.to(self._unet_dtype()), t_start
 
+    # -- inpainting ------------------------------------------------------------
+
+    def _prepare_mask(self, mask) -> torch.Tensor:
+        """A float tensor [H,W] / [1,H,W] / [1,1,H,W] in [0, 1], a uint8 [H,W]
+        numpy array (0..255) or a PIL image (converted to "L") -> the binary
+        pixel mask, fp32 [1,1,H,W] on the model device: 1 (values >= 0.5)
+        means repaint. H, W must be DistriConfig's: nothing is resized."""
+        cfg = self.distri_config
+        if not torch.is_tensor(mask):
+            import numpy as np
+
+            if not isinstance(mask, np.ndarray):
+                try:
+                    from PIL import Image
+                except ImportError:
+                    Image = None
+                if Image is None or not isinstance(mask, Image.Image):
+                    raise TypeError(f"mask: unsupported type {type(mask).__name__}")
+                mask = np.array(mask.convert("L"))
+            if mask.dtype != np.uint8 or mask.ndim != 2:
+                raise ValueError("mask: a numpy mask must be uint8 [H, W], got "
+                                 f"{mask.dtype} {mask.shape}")
+            mask = torch.from_numpy(np.ascontiguousarray(mask)).float() / 255.0
+        elif not mask.is_floating_point():
+            raise ValueError("mask: a tensor mask must be floating point in [0, 1]")
+        if mask.dim() not in (2, 3, 4) or any(s != 1 for s in mask.shape[:-2]):
+            raise ValueError(f"mask: expected [H,W], [1,H,W] or [1,1,H,W], got {tuple(mask.shape)}")
+        if tuple(mask.shape[-2:]) != (cfg.height, cfg.width):
+            raise ValueError(
+                f"mask is {mask.shape[-2]}x{mask.shape[-1]} but the pipeline is built for "
+                f"{cfg.height}x{cfg.width} (DistriConfig); resize it first")
+        mask = mask.reshape(1, 1, cfg.height, cfg.width)
+        return (mask.float() >= 0.5).float().to(cfg.device)
+
+    @staticmethod
+    def _latent_mask(pixel_mask: torch.Tensor) -> torch.Tensor:
+        """The mask at latent resolution by nearest sampling: latent pixel
+        (i, j) takes mask pixel (8i, 8j), which is what ``F.interpolate`` to
+        (H/8, W/8) in its default nearest mode gives (the diffusers rule)."""
+        return pixel_mask[..., ::8, ::8].contiguous()
+
+    def _inpaint_latents(self, image, mask, strength: float, num_inference_steps: int,
+                         generator):
+        """Returns (latents, t_start, inpaint): the start latents, the first
+        executed step and what every step's blend needs. One generator gives,
+        in this order, the posterior sample of ``image``, the posterior sample
+        of the masked image (9-channel U-Nets only) and the noise. strength < 1
+        starts as img2img does, from the image noised to the first executed
+        timestep; strength = 1 starts from pure noise, and the same noise
+        tensor re-noises the known region at every step."""
+        t_start = img2img_start(num_inference_steps, strength)
+        pixels = self._prepare_image(image)
+        pixel_mask = self._prepare_mask(mask)
+        if generator is None:
+            generator = torch.Generator().manual_seed(0)  # same on every rank
+        from .utils.tracing import trace_range
+
+        dtype = self._unet_dtype()
+        inpaint = {"mask": self._latent_mask(pixel_mask)}
+        with trace_range("vae_encode"):
+            inpaint["init"] = self.vae_encoder.encode(pixels, generator=generator).float()
+            if self.unet.config.in_channels == 9:
+                keep = (pixel_mask < 0.5).to(pixels.dtype)
+                masked = self.vae_encoder.encode(pixels * keep, generator=generator)
+                inpaint["masked_latents"] = masked.to(dtype)
+                inpaint["mask_in"] = inpaint["mask"].to(dtype)
+        init = inpaint["init"]
+        device = generator.device if hasattr(generator, "device") else torch.device("cpu")
+        noise = torch.randn(init.shape, generator=generator, dtype=torch.float32, device=device)
+        inpaint["init_noise"] = noise.to(init.device)
+        self.scheduler.set_timesteps(num_inference_steps, device=None)
+        if strength < 1:
+            latents = self.scheduler.add_noise(init, inpaint["init_noise"],
+                                               self.scheduler.timesteps[t_start]).to(dtype)
+        else:
+            latents = inpaint["init_noise"].to(dtype) * self.scheduler.init_noise_sigma
+        return latents, t_start, inpaint
+
     def _denoise(self, latents, prompt_embeds, added_cond_kwargs, num_inference_steps,
-                 guidance_scale, t_start: int = 0):
+                 guidance_scale, t_start: int = 0, inpaint: dict | None = None):
         """``t_start > 0`` (img2img) runs the last n - t_start steps only. The
         U-Net counter is 0 at the first step that actually runs, so the
         ``warmup_steps`` synchronous steps of displaced patch parallelism are
         counted from there, and the captured graphs and ``_graph_counters``
-        are the text-to-image ones."""
+        are the text-to-image ones.
+
+        ``inpaint`` (from ``_inpaint_latents``) ends every step in the
+        scheduler's ``masked_step`` and, with a 9-channel U-Net, assembles the
+        U-Net input with ``ops.inpaint_unet_input``. Every rank holds the full
+        latents, so the blend is replicated work like the step itself."""
         cfg = self.distri_config
         do_cfg = cfg.do_classifier_free_guidance
         from .utils.tracing import trace_range
@@ -274,15 +365,24 @@ class _DistriPipelineBase:
         self.unet.set_counter(0)
         for i, t in enumerate(_maybe_tqdm(self.scheduler.timesteps, self._progress)):
             with trace_range(f"denoise_step_{i}"):
-                latent_in = torch.cat([latents] * 2) if do_cfg else latents
-                latent_in = self.scheduler.scale_model_input(latent_in, t)
+                if inpaint is not None and "masked_latents" in inpaint:
+                    latent_in = ops.inpaint_unet_input(
+                        latents, inpaint["mask_in"], inpaint["masked_latents"],
+                        self.scheduler.model_input_scale(t), 2 if do_cfg else 1)
+                else:
+                    latent_in = torch.cat([latents] * 2) if do_cfg else latents
+                    latent_in = self.scheduler.scale_model_input(latent_in, t)
                 noise = self.unet(
                     latent_in,
                     t.to(cfg.device) if torch.is_tensor(t) else t,
                     prompt_embeds,
                     added_cond_kwargs,
                 )
-                if do_cfg and hasattr(self.scheduler, "guided_step"):
+                if inpaint is not None:
+                    latents = self.scheduler.masked_step(
+                        noise, t, latents, guidance_scale, inpaint["mask"], inpaint["init"],
+                        inpaint["init_noise"])
+                elif do_cfg and hasattr(self.scheduler, "guided_step"):
                     latents = self.scheduler.guided_step(noise, t, latents, guidance_scale)
                 else:
                     if do_cfg:
@@ -292,17 +392,26 @@ class _DistriPipelineBase:
         return latents
 
     def _generate(self, embeds, added_cond_kwargs, num_inference_steps, guidance_scale,
-                  generator, output_type, image, strength):
+                  generator, output_type, image, strength, mask=None):
         """The tail both pipelines share once the prompt is encoded: initial
-        (or img2img) latents -> denoise -> decode."""
-        t_start = 0
+        (or img2img, or inpaint) latents -> denoise -> decode. ``strength``
+        None is 0.3 for img2img and 1.0 for inpainting."""
+        if mask is not None and image is None:
+            raise ValueError("mask= needs image=: inpainting repaints part of an image")
+        if self.unet.config.in_channels == 9 and mask is None:
+            raise ValueError("a 9-channel inpaint U-Net needs image= and mask=")
+        t_start, inpaint = 0, None
         if image is None:
             latents = self._prepare_latents(1, generator)
+        elif mask is None:
+            latents, t_start = self._img2img_latents(
+                image, 0.3 if strength is None else strength, num_inference_steps, generator)
         else:
-            latents, t_start = self._img2img_latents(image, strength, num_inference_steps,
-                                                     generator)
+            latents, t_start, inpaint = self._inpaint_latents(
+                image, mask, 1.0 if strength is None else strength, num_inference_steps,
+                generator)
         latents = self._denoise(latents, embeds, added_cond_kwargs, num_inference_steps,
-                                guidance_scale, t_start)
+                                guidance_scale, t_start, inpaint)
         return self._decode(latents, output_type)
 
     def _decode(self, latents: torch.Tensor, output_type: str):
@@ -435,7 +544,8 @@ class DistriSDXLPipeline(_DistriPipelineBase):
             unet_cfg, vae_cfg = TINY_UNET, TINY_VAE
             clip1_cfg, clip2_cfg = TINY_CLIP, TINY_CLIP
         else:
-            unet_cfg, vae_cfg = SDXL_UNET, SDXL_VAE
+            unet_cfg = SDXL_INPAINT_UNET if preset == "sdxl-inpaint" else SDXL_UNET
+            vae_cfg = SDXL_VAE
             clip1_cfg, clip2_cfg = CLIP_VIT_L, OPEN_CLIP_BIG_G
         tokenizer = _resolve_tokenizer(pretrained, clip1_cfg.vocab_size,
                                        allow_simple=allow_simple)
@@ -491,7 +601,7 @@ class DistriSDXLPipeline(_DistriPipelineBase):
         embeds, pooled = self.encode_prompt("", do_classifier_free_guidance=False)
         embeds = embeds.repeat(batch_size, 1, 1).to(self._unet_dtype())
         pooled = pooled.repeat(batch_size, 1).to(self._unet_dtype())
-        latents = self._prepare_latents(batch_size, None)
+        latents = self._prepare_latents(batch_size, None, self.unet.config.in_channels)
         return {
             "sample": latents,
             "timestep": torch.zeros((), dtype=torch.float32, device=self.distri_config.device),
@@ -509,7 +619,8 @@ class DistriSDXLPipeline(_DistriPipelineBase):
         generator: torch.Generator | None = None,
         output_type: str = "pil",
         image=None,
-        strength: float = 0.3,
+        strength: float | None = None,
+        mask=None,
         **kwargs,
     ):
         """Text-to-image, or with ``image=`` img2img (SDEdit): the image (a
@@ -518,7 +629,18 @@ class DistriSDXLPipeline(_DistriPipelineBase):
         to ``strength`` and denoised over the last ``int(steps * strength)``
         steps. The displaced-patch warmup counts from the first step that
         runs (see ``_denoise``). The added time ids are the text-to-image
-        ones; there is no refiner aesthetic score."""
+        ones; there is no refiner aesthetic score.
+
+        With ``mask=`` as well it inpaints: the mask (a float tensor [H,W] /
+        [1,H,W] / [1,1,H,W] in [0, 1], a uint8 [H,W] numpy array or a PIL
+        image, at the same size) is binarised at 0.5, 1 meaning repaint, and
+        taken to latent resolution by nearest sampling (``mask[::8, ::8]``).
+        After every step the known region is replaced by the image latents
+        noised to the next timestep (and by the clean ones after the last),
+        so it comes out as encoded. A 9-channel inpaint U-Net (preset
+        ``"sdxl-inpaint"``) is also fed the mask and the masked-image
+        latents. ``strength`` defaults to 0.3 for img2img and to 1.0, a start
+        from pure noise, with a mask."""
         assert "height" not in kwargs and "width" not in kwargs, (
             "height/width are fixed by DistriConfig (the comm buffers and "
             "graphs are sized for them)"
@@ -534,7 +656,7 @@ class DistriSDXLPipeline(_DistriPipelineBase):
         pooled = pooled.to(self._unet_dtype())
         added = self._added_cond(embeds.shape[0], pooled)
         return self._generate(embeds, added, num_inference_steps, guidance_scale, generator,
-                              output_type, image, strength)
+                              output_type, image, strength, mask)
 
 
 class DistriSDPipeline(_DistriPipelineBase):
@@ -572,7 +694,8 @@ class DistriSDPipeline(_DistriPipelineBase):
 
             unet_cfg, vae_cfg, clip_cfg = SD21_UNET, SD_VAE, OPEN_CLIP_VIT_H
         else:
-            unet_cfg, vae_cfg, clip_cfg = SD15_UNET, SD_VAE, CLIP_VIT_L
+            unet_cfg = SD15_INPAINT_UNET if preset == "sd15-inpaint" else SD15_UNET
+            vae_cfg, clip_cfg = SD_VAE, CLIP_VIT_L
         tokenizer = _resolve_tokenizer(pretrained, clip_cfg.vocab_size,
                                        allow_simple=allow_simple)
         unet_cfg = kwargs.pop("unet_config", unet_cfg)
@@ -603,7 +726,7 @@ class DistriSDPipeline(_DistriPipelineBase):
     def _build_static_inputs(self, batch_size: int) -> dict:
         embeds = self.encode_prompt("", do_classifier_free_guidance=False)
         embeds = embeds.repeat(batch_size, 1, 1).to(self._unet_dtype())
-        latents = self._prepare_latents(batch_size, None)
+        latents = self._prepare_latents(batch_size, None, self.unet.config.in_channels)
         return {
             "sample": latents,
             "timestep": torch.zeros((), dtype=torch.float32, device=self.distri_config.device),
@@ -621,11 +744,13 @@ class DistriSDPipeline(_DistriPipelineBase):
         generator: torch.Generator | None = None,
         output_type: str = "pil",
         image=None,
-        strength: float = 0.3,
+        strength: float | None = None,
+        mask=None,
         **kwargs,
     ):
-        """Text-to-image, or img2img with ``image=`` / ``strength=`` (see
-        ``DistriSDXLPipeline.__call__``)."""
+        """Text-to-image, img2img with ``image=`` / ``strength=``, or
+        inpainting with ``mask=`` as well (see ``DistriSDXLPipeline.__call__``;
+        the 9-channel preset here is ``"sd15-inpaint"``)."""
         assert "height" not in kwargs and "width" not in kwargs
         cfg = self.distri_config
         if not cfg.do_classifier_free_guidance:
@@ -633,4 +758,4 @@ class DistriSDPipeline(_DistriPipelineBase):
         do_cfg = cfg.do_classifier_free_guidance
         embeds = self.encode_prompt(prompt, negative_prompt, do_cfg).to(self._unet_dtype())
         return self._generate(embeds, None, num_inference_steps, guidance_scale, generator,
-                              output_type, image, strength)
+                              output_type, image, strength, mask)

@@ -56,6 +56,60 @@ class SchedulerBase:
         out = acp.sqrt() * sample.float() + (1 - acp).sqrt() * noise.float().to(sample.device)
         return out.to(sample.dtype)
 
+    # -- inpainting: the step blended with the re-noised known region ---------
+
+    def model_input_scale(self, timestep=None) -> float:
+        """The divisor ``scale_model_input`` applies at the current step."""
+        return 1.0
+
+    def _next_timestep(self, timestep):
+        """The entry after ``timestep`` in the running list, None at its end."""
+        idx = int((self.timesteps == float(timestep)).nonzero()[0])
+        return self.timesteps[idx + 1] if idx + 1 < len(self.timesteps) else None
+
+    def _known_coeffs(self, timestep) -> tuple[float, float]:
+        """(sa, sb) of known = sa*init + sb*init_noise: the init latents noised
+        to the next timestep of the running list, and the clean init latents
+        (1, 0) after the last step (the diffusers rule)."""
+        t_next = self._next_timestep(timestep)
+        if t_next is None:
+            return 1.0, 0.0
+        acp = float(self.alphas_cumprod[int(t_next)])
+        return acp ** 0.5, (1 - acp) ** 0.5
+
+    def masked_step(self, noise: torch.Tensor, timestep, sample: torch.Tensor,
+                    guidance_scale: float, mask: torch.Tensor, init: torch.Tensor,
+                    init_noise: torch.Tensor) -> torch.Tensor:
+        """One inpaint step: what ``guided_step`` (noise is the [uncond; cond]
+        pair) or ``step`` (noise has sample's batch; guidance_scale is not
+        read) computes, then
+
+            out = m * x' + (1 - m) * known
+
+        with known = ``add_noise(init, init_noise, t_next)``, or init itself
+        after the last step. mask (1 = repaint) has one value per latent
+        pixel; init and init_noise are fp32 [1,C,h,w]. The scheduler state
+        advances as in an unmasked step. One fused kernel on GPU; elsewhere
+        the composition of ``step`` and ``add_noise`` in fp32."""
+        from ..ops import use_hip
+
+        if use_hip(sample):
+            return self._masked_step_native(noise, timestep, sample, guidance_scale, mask, init,
+                                            init_noise)
+        from ..ops.eager import _cfg_eps
+
+        t_next = self._next_timestep(timestep)  # before step() moves on
+        eps = _cfg_eps(noise, sample, guidance_scale)
+        xp = self.step(eps, timestep, sample.float())
+        init = init.float().to(sample.device)
+        known = init if t_next is None else self.add_noise(init, init_noise, t_next)
+        m = mask.float().to(sample.device).reshape(1, 1, *sample.shape[2:])
+        return (m * xp + (1.0 - m) * known).to(sample.dtype)
+
+    def _masked_step_native(self, noise, timestep, sample, guidance_scale, mask, init,
+                            init_noise) -> torch.Tensor:
+        raise NotImplementedError
+
     def set_begin_index(self, t_start: int) -> None:
         """Start the schedule at index ``t_start`` of the list that
         ``set_timesteps(n)`` made: ``timesteps`` becomes its last n - t_start

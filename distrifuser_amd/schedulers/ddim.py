@@ -36,17 +36,30 @@ class DDIMScheduler(SchedulerBase):
         # otherwise exposed every denoise step.
         from ..ops import hip_ext, use_hip
 
+        if use_hip(noise):
+            ca, cb = self._affine_coeffs(timestep)
+            return hip_ext().cfg_affine_step(noise, sample, guidance_scale, ca, cb)
+        nu, nc = noise.float().chunk(2)
+        eps = nu + guidance_scale * (nc - nu)
+        return self.step(eps, timestep, sample)
+
+    def _affine_coeffs(self, timestep) -> tuple[float, float]:
+        # x' = sqrt(a_p) * (x - sqrt(1-a_t) eps)/sqrt(a_t) + sqrt(1-a_p) eps
+        #    = ca * x + cb * eps
         t = int(timestep)
         prev_t = t - self.num_train_timesteps // self.num_inference_steps
         acp = self.alphas_cumprod
         alpha_t = float(acp[t])
         alpha_prev = float(acp[prev_t] if prev_t >= 0 else acp[0])
-        if use_hip(noise):
-            # x' = sqrt(a_p) * (x - sqrt(1-a_t) eps)/sqrt(a_t) + sqrt(1-a_p) eps
-            #    = ca * x + cb * eps
-            ca = (alpha_prev / alpha_t) ** 0.5
-            cb = (1 - alpha_prev) ** 0.5 - ca * (1 - alpha_t) ** 0.5
-            return hip_ext().cfg_affine_step(noise, sample, guidance_scale, ca, cb)
-        nu, nc = noise.float().chunk(2)
-        eps = nu + guidance_scale * (nc - nu)
-        return self.step(eps, timestep, sample)
+        ca = (alpha_prev / alpha_t) ** 0.5
+        cb = (1 - alpha_prev) ** 0.5 - ca * (1 - alpha_t) ** 0.5
+        return ca, cb
+
+    def _masked_step_native(self, noise, timestep, sample, guidance_scale, mask, init,
+                            init_noise) -> torch.Tensor:
+        from ..ops import masked_affine_step
+
+        ca, cb = self._affine_coeffs(timestep)
+        sa, sb = self._known_coeffs(timestep)
+        return masked_affine_step(noise, sample, init, init_noise, mask, guidance_scale, ca, cb,
+                                  sa, sb)

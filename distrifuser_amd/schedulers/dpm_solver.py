@@ -86,6 +86,17 @@ class DPMSolverMultistepScheduler(SchedulerBase):
             eps = nu + guidance_scale * (nc - nu)
             return self.step(eps, timestep, sample)
 
+        first, coeffs = self._affine_coeffs(timestep)
+        prev, x0 = hip_ext().cfg_dpm_step(
+            noise, sample, None if first else self._x0_prev, guidance_scale, *coeffs)
+        self._x0_prev = x0
+        self._t_prev = int(timestep)
+        self._step_index += 1
+        return prev
+
+    def _affine_coeffs(self, timestep) -> tuple[bool, tuple[float, ...]]:
+        """(first, (ca, cb, cc, cx, ce)) of the step at ``timestep``; first:
+        a first-order step, which reads no x0_prev."""
         t = int(timestep)
         t_prev = self._prev_timestep(t)
         a_t, s_t, l_t = (float(self.alpha_t[t]), float(self.sigma_t[t]),
@@ -109,10 +120,17 @@ class DPMSolverMultistepScheduler(SchedulerBase):
         cb = cprime * s_t / a_t
         cx = 1.0 / a_t
         ce = -s_t / a_t
-        prev, x0 = hip_ext().cfg_dpm_step(
-            noise, sample, None if first else self._x0_prev, guidance_scale,
-            ca, cb, cc, cx, ce)
+        return first, (ca, cb, cc, cx, ce)
+
+    def _masked_step_native(self, noise, timestep, sample, guidance_scale, mask, init,
+                            init_noise) -> torch.Tensor:
+        from ..ops import masked_dpm_step
+
+        first, coeffs = self._affine_coeffs(timestep)
+        sa, sb = self._known_coeffs(timestep)
+        prev, x0 = masked_dpm_step(noise, sample, None if first else self._x0_prev, init,
+                                   init_noise, mask, guidance_scale, *coeffs, sa, sb)
         self._x0_prev = x0
-        self._t_prev = t
+        self._t_prev = int(timestep)
         self._step_index += 1
         return prev

@@ -66,3 +66,24 @@ class EulerDiscreteScheduler(SchedulerBase):
         nu, nc = noise.float().chunk(2)
         eps = nu + guidance_scale * (nc - nu)
         return self.step(eps, timestep, sample)
+
+    # -- inpainting --------------------------------------------------------------
+
+    def model_input_scale(self, timestep=None) -> float:
+        sigma = self.sigmas[self._step_index]
+        return float((sigma**2 + 1) ** 0.5)
+
+    def _known_coeffs(self, timestep) -> tuple[float, float]:
+        # known = init + sigma_next * init_noise; sigma = 0 after the last step
+        last = self._step_index + 1 >= len(self.timesteps)
+        return 1.0, 0.0 if last else float(self.sigmas[self._step_index + 1])
+
+    def _masked_step_native(self, noise, timestep, sample, guidance_scale, mask, init,
+                            init_noise) -> torch.Tensor:
+        from ..ops import masked_affine_step
+
+        sa, sb = self._known_coeffs(timestep)
+        cb = float(self.sigmas[self._step_index + 1] - self.sigmas[self._step_index])
+        self._step_index += 1
+        return masked_affine_step(noise, sample, init, init_noise, mask, guidance_scale, 1.0, cb,
+                                  sa, sb)
