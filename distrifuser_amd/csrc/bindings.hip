@@ -187,19 +187,53 @@ at::Tensor geglu(const at::Tensor& h_) {
     return out;
 }
 
+// The guidance_rescale factor of a step, or null: one fp32 on the GPU, for a
+// [2,C,h,w] CFG pair and x [1,C,h,w] only
+const float* rescale_factor(const char* op, const c10::optional<at::Tensor>& factor,
+                            const at::Tensor& noise, const at::Tensor& x) {
+    if (!factor.has_value()) return nullptr;
+    TORCH_CHECK(factor->is_cuda() && factor->scalar_type() == at::kFloat && factor->numel() == 1,
+                op, ": factor must be one fp32 value on the GPU");
+    TORCH_CHECK(noise.dim() == 4 && noise.size(0) == 2 && noise.numel() == 2 * x.numel(), op,
+                ": a rescale factor needs the [2,C,h,w] CFG pair as noise");
+    TORCH_CHECK(x.dim() == 4 && x.size(0) == 1, op,
+                ": a rescale factor needs x [1,C,h,w] (one sample)");
+    return factor->data_ptr<float>();
+}
+
+// r = phi * std(nc) / std(nu + g*(nc - nu)) + (1 - phi) over the one sample of
+// the [2,C,h,w] CFG pair -> fp32 [1]; two launches, the same bits on every run
+at::Tensor guidance_rescale_factor(const at::Tensor& noise, double g, double phi) {
+    TORCH_CHECK(noise.is_cuda() && noise.dim() == 4 && noise.size(0) == 2,
+                "guidance_rescale_factor: noise must be the CUDA [2,C,h,w] CFG pair");
+    auto n = noise.contiguous();
+    const int64_t total = n.numel() / 2;
+    TORCH_CHECK(total > 0, "guidance_rescale_factor: empty noise");
+    const auto f32 = n.options().dtype(at::kFloat);
+    auto ws = at::empty({(long)cfg_moments_blocks(total), 4}, f32);
+    auto factor = at::empty({1}, f32);
+    launch_guidance_rescale_factor(
+        n.data_ptr(), reinterpret_cast<const char*>(n.data_ptr()) + total * n.element_size(),
+        (float)g, (float)phi, total, ws.data_ptr<float>(), factor.data_ptr<float>(), dtype_of(n),
+        cur_stream());
+    return factor;
+}
+
 at::Tensor cfg_affine_step(const at::Tensor& noise, const at::Tensor& x, double g, double ca,
-                           double cb) {
+                           double cb, const c10::optional<at::Tensor>& factor) {
     // noise: [2, C, H, W] = [uncond; cond]; x: [1, C, H, W]; out = ca*x + cb*eps
     TORCH_CHECK(noise.is_cuda() && noise.size(0) == 2);
     auto n = noise.contiguous();
     auto xc = x.contiguous();
     TORCH_CHECK(xc.numel() * 2 == n.numel());
+    const float* fp = rescale_factor("cfg_affine_step", factor, noise, x);
     auto out = at::empty_like(xc);
     const int64_t total = xc.numel();
     launch_cfg_affine_step(
         n.data_ptr(),
         reinterpret_cast<const char*>(n.data_ptr()) + total * n.element_size(), xc.data_ptr(),
-        out.data_ptr(), (float)g, (float)ca, (float)cb, total, dtype_of(xc), cur_stream());
+        out.data_ptr(), (float)g, (float)ca, (float)cb, total, dtype_of(xc), cur_stream(),
+        nullptr, fp);
     return out;
 }
 
@@ -240,12 +274,13 @@ MaskedStepArgs masked_step_args(const char* op, const at::Tensor& noise, const a
 at::Tensor masked_affine_step(const at::Tensor& noise, const at::Tensor& x,
                               const at::Tensor& init, const at::Tensor& init_noise,
                               const at::Tensor& mask, double g, double ca, double cb, double sa,
-                              double sb) {
+                              double sb, const c10::optional<at::Tensor>& factor) {
     auto a = masked_step_args("masked_affine_step", noise, x, init, init_noise, mask, sa, sb);
+    const float* fp = rescale_factor("masked_affine_step", factor, noise, x);
     auto out = at::empty_like(a.x);
     launch_cfg_affine_step(a.n.data_ptr(), a.nc, a.x.data_ptr(), out.data_ptr(), (float)g,
                            (float)ca, (float)cb, a.x.numel(), dtype_of(a.x), cur_stream(),
-                           &a.blend);
+                           &a.blend, fp);
     return out;
 }
 
@@ -549,7 +584,7 @@ at::Tensor conv3x3(const at::Tensor& x, const at::Tensor& wp,
 std::vector<at::Tensor> dpm_step(const at::Tensor& n, const void* nc, const at::Tensor& xc,
                                  const c10::optional<at::Tensor>& x0_prev, double g, double ca,
                                  double cb, double cc, double cx, double ce,
-                                 const MaskBlend* blend) {
+                                 const MaskBlend* blend, const float* factor) {
     const void* pp = nullptr;
     at::Tensor p;
     if (x0_prev.has_value()) {
@@ -562,20 +597,22 @@ std::vector<at::Tensor> dpm_step(const at::Tensor& n, const void* nc, const at::
     auto x0 = at::empty_like(xc, xc.options().dtype(at::kFloat));
     launch_cfg_dpm_step(n.data_ptr(), nc, xc.data_ptr(), pp, out.data_ptr(), x0.data_ptr(),
                         (float)g, (float)ca, (float)cb, (float)cc, (float)cx, (float)ce,
-                        xc.numel(), dtype_of(xc), cur_stream(), blend);
+                        xc.numel(), dtype_of(xc), cur_stream(), blend, factor);
     return {out, x0};
 }
 
 std::vector<at::Tensor> cfg_dpm_step(const at::Tensor& noise, const at::Tensor& x,
                                      const c10::optional<at::Tensor>& x0_prev, double g,
-                                     double ca, double cb, double cc, double cx, double ce) {
+                                     double ca, double cb, double cc, double cx, double ce,
+                                     const c10::optional<at::Tensor>& factor) {
     TORCH_CHECK(noise.is_cuda() && noise.size(0) == 2);
     auto n = noise.contiguous();
     auto xc = x.contiguous();
     TORCH_CHECK(xc.numel() * 2 == n.numel());
     const void* nc =
         reinterpret_cast<const char*>(n.data_ptr()) + xc.numel() * n.element_size();
-    return dpm_step(n, nc, xc, x0_prev, g, ca, cb, cc, cx, ce, nullptr);
+    return dpm_step(n, nc, xc, x0_prev, g, ca, cb, cc, cx, ce, nullptr,
+                    rescale_factor("cfg_dpm_step", factor, noise, x));
 }
 
 // cfg_dpm_step with the inpaint blend on prev; x0 is the unmasked step's
@@ -583,9 +620,11 @@ std::vector<at::Tensor> masked_dpm_step(const at::Tensor& noise, const at::Tenso
                                         const c10::optional<at::Tensor>& x0_prev,
                                         const at::Tensor& init, const at::Tensor& init_noise,
                                         const at::Tensor& mask, double g, double ca, double cb,
-                                        double cc, double cx, double ce, double sa, double sb) {
+                                        double cc, double cx, double ce, double sa, double sb,
+                                        const c10::optional<at::Tensor>& factor) {
     auto a = masked_step_args("masked_dpm_step", noise, x, init, init_noise, mask, sa, sb);
-    return dpm_step(a.n, a.nc, a.x, x0_prev, g, ca, cb, cc, cx, ce, &a.blend);
+    return dpm_step(a.n, a.nc, a.x, x0_prev, g, ca, cb, cc, cx, ce, &a.blend,
+                    rescale_factor("masked_dpm_step", factor, noise, x));
 }
 
 at::Tensor layer_norm(const at::Tensor& x_, const at::Tensor& w_, const at::Tensor& b_,
@@ -679,7 +718,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("geglu", &geglu, "a * gelu(gate) over last-dim halves");
     m.def("gn_merge_stats", &gn_merge_stats,
           "merge stale peer GN moments with fresh local ones (one launch)");
-    m.def("cfg_affine_step", &cfg_affine_step, "fused CFG combine + affine scheduler update");
+    m.def("guidance_rescale_factor", &guidance_rescale_factor,
+          "guidance_rescale factor phi*std(cond)/std(cfg) + 1 - phi of a CFG pair -> fp32 [1]");
+    m.def("cfg_affine_step", &cfg_affine_step,
+          "fused CFG combine + affine scheduler update; factor: the guidance_rescale factor",
+          pybind11::arg("noise"), pybind11::arg("x"), pybind11::arg("g"), pybind11::arg("ca"),
+          pybind11::arg("cb"), pybind11::arg("factor") = pybind11::none());
     m.def("flash_attention", &flash_attention, "bf16/fp16 flash attention (chunked stale KV)");
     m.def("flash_attention_ext", &flash_attention_ext,
           "flash attention with split-KV and optional log-sum-exp -> [out] or [out, lse]",
@@ -691,11 +735,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "merge fp32 attention partials by their log-sum-exp -> [out, lse]",
           pybind11::arg("o_parts"), pybind11::arg("lse_parts"), pybind11::arg("out_bf16") = true,
           pybind11::arg("out_dtype") = pybind11::none());
-    m.def("cfg_dpm_step", &cfg_dpm_step, "fused CFG + DPM-Solver++(2M) update -> (prev, x0)");
+    m.def("cfg_dpm_step", &cfg_dpm_step, "fused CFG + DPM-Solver++(2M) update -> (prev, x0)",
+          pybind11::arg("noise"), pybind11::arg("x"), pybind11::arg("x0_prev"),
+          pybind11::arg("g"), pybind11::arg("ca"), pybind11::arg("cb"), pybind11::arg("cc"),
+          pybind11::arg("cx"), pybind11::arg("ce"), pybind11::arg("factor") = pybind11::none());
     m.def("masked_affine_step", &masked_affine_step,
-          "inpaint: (CFG +) affine scheduler update blended with the re-noised init latents");
+          "inpaint: (CFG +) affine scheduler update blended with the re-noised init latents",
+          pybind11::arg("noise"), pybind11::arg("x"), pybind11::arg("init"),
+          pybind11::arg("init_noise"), pybind11::arg("mask"), pybind11::arg("g"),
+          pybind11::arg("ca"), pybind11::arg("cb"), pybind11::arg("sa"), pybind11::arg("sb"),
+          pybind11::arg("factor") = pybind11::none());
     m.def("masked_dpm_step", &masked_dpm_step,
-          "inpaint: (CFG +) DPM-Solver++(2M) update, prev blended -> (prev, x0)");
+          "inpaint: (CFG +) DPM-Solver++(2M) update, prev blended -> (prev, x0)",
+          pybind11::arg("noise"), pybind11::arg("x"), pybind11::arg("x0_prev"),
+          pybind11::arg("init"), pybind11::arg("init_noise"), pybind11::arg("mask"),
+          pybind11::arg("g"), pybind11::arg("ca"), pybind11::arg("cb"), pybind11::arg("cc"),
+          pybind11::arg("cx"), pybind11::arg("ce"), pybind11::arg("sa"), pybind11::arg("sb"),
+          pybind11::arg("factor") = pybind11::none());
     m.def("inpaint_unet_input", &inpaint_unet_input,
           "inpaint U-Net input [copies,9,h,w] = [latents / scale, mask, masked-image latents]");
     m.def("layer_norm", &layer_norm, "bf16/fp16 fused LayerNorm");

@@ -70,13 +70,29 @@ struct MaskBlend {
     int64_t hw;
 };
 
+// ---- guidance_rescale factor ---------------------------------------------------
+// factor[0] = phi * std(nc) / std(eps) + (1 - phi), eps = nu + g*(nc - nu), both
+// standard deviations over the `total` elements of the one sample; fp32 sums.
+// Two launches: cfg_moments_blocks(total) blocks each store four partial sums
+// to a row of ws, fp32 [blocks][4] (no initialisation needed), and one block
+// adds the rows in index order. The block count depends on total alone, so
+// the factor is the same bits on every run and device.
+int cfg_moments_blocks(int64_t total);
+void launch_guidance_rescale_factor(const void* noise_u, const void* noise_c, float g, float phi,
+                                    int64_t total, float* ws, float* factor, int dtype,
+                                    hipStream_t stream);
+
 // ---- fused CFG + scheduler step (affine: out = ca*x + cb*eps) ---------------
 // blend != null: the masked step, total = C*hw; noise_c may then be null (no
 // CFG pair: eps = noise_u, g is not read). Its 16-byte path needs hw a
 // multiple of the vector width and 16-byte aligned pointers.
+// factor != null (one fp32 on the device, noise_c not null): eps is replaced
+// by round(factor[0] * eps) before the update. A factor of 1 gives the bits
+// of the call without one.
 void launch_cfg_affine_step(const void* noise_u, const void* noise_c, const void* x, void* out,
                             float g, float ca, float cb, int64_t total, int dtype,
-                            hipStream_t stream, const MaskBlend* blend = nullptr);
+                            hipStream_t stream, const MaskBlend* blend = nullptr,
+                            const float* factor = nullptr);
 
 // ---- inpaint U-Net input assembly --------------------------------------------
 // out [copies, 9, hw]: channels 0..3 = latents [4, hw] / scale, channel 4 =
@@ -119,11 +135,11 @@ void launch_conv3x3(const Conv3x3Params& p, int stride, int dtype, hipStream_t s
 // ---- fused CFG + DPM-Solver++(2M) step --------------------------------------
 // out = ca*x + cb*eps + cc*x0_prev (x0_prev may be null); x0_out = cx*x + ce*eps
 // blend != null: out is blended as in the masked affine step (nc may be null);
-// x0_out is not.
+// x0_out is not. factor as in the affine step: out and x0_out both use eps_r.
 void launch_cfg_dpm_step(const void* nu, const void* nc, const void* x, const void* x0_prev,
                          void* out, void* x0_out, float g, float ca, float cb, float cc,
                          float cx, float ce, int64_t total, int dtype, hipStream_t stream,
-                         const MaskBlend* blend = nullptr);
+                         const MaskBlend* blend = nullptr, const float* factor = nullptr);
 
 // ---- fused (residual +) LayerNorm (bf16 or fp16, C <= 2048, C % 8 == 0) -------------
 // y = LN(x [+ res]); when res != null and sum_out != null, x+res is also

@@ -23,8 +23,26 @@
 // (one fp32 value per latent element) and m (one per pixel, shared by the
 // channels) are read-only. A masked step also runs without a CFG pair:
 // noise_c null means eps = nu.
+//
+// guidance_rescale (the RESCALE axis of both step kernels) scales the CFG
+// result towards the cond branch's standard deviation, both taken over the
+// one sample (C, H, W):
+//
+//   r     = phi * std(nc) / std(eps) + (1 - phi)
+//   eps_r = r * eps                        (a rounding of its own)
+//
+// and the step is formed from eps_r. r comes from two launches before the
+// step: cfg_moments_kernel writes each CHUNK's four partial sums to its own
+// workspace row, cfg_rescale_finalize_kernel adds the rows in index order.
+// No atomics, and a block count that depends on the element count alone: the
+// factor is the same bits on every run and every device.
 
 #include "dispatch.h"
+
+// elements per block of cfg_moments_kernel, a constant of the arithmetic (it
+// fixes the summation tree): 8 blocks at 1024^2, 113 at 3840^2
+constexpr int64_t CFG_MOMENTS_CHUNK = 8192;
+constexpr int CFG_MOMENTS_BLOCK = 256;
 
 namespace {
 
@@ -56,19 +74,32 @@ __device__ __forceinline__ float affine_xp(float ca, float x, float cb, float ep
     return s + t;
 }
 
+// eps_r of the RESCALE kernels: never contracted into the step's products, so
+// f == 1 returns eps and with it the instantiation without RESCALE
+__device__ __forceinline__ float rescale_eps(float f, float eps) {
+#pragma clang fp contract(off)
+    const float r = f * eps;
+    return r;
+}
+
 __device__ __forceinline__ float mask_blend(float xp, float m, float init, float init_noise,
                                             float sa, float sb) {
     const float known = sa * init + sb * init_noise;
     return m * xp + (1.f - m) * known;
 }
 
-// VEC && MASKED: hw % V == 0, so a vector never straddles a plane
-template <typename T, bool VEC, bool MASKED>
+// VEC && MASKED: hw % V == 0, so a vector never straddles a plane. MASKED and
+// RESCALE share the explicitly rounded form; RESCALE reads *factor, noise_c is
+// then never null.
+template <typename T, bool VEC, bool MASKED, bool RESCALE>
 __global__ void cfg_affine_step_kernel(const T* __restrict__ noise_u,
                                        const T* __restrict__ noise_c, const T* __restrict__ x,
                                        T* __restrict__ out, float g, float ca, float cb,
-                                       int64_t total, MaskBlend bl) {
+                                       int64_t total, MaskBlend bl,
+                                       const float* __restrict__ factor) {
     constexpr int V = VEC ? VecN<T>::value : 1;
+    float f = 1.f;
+    if constexpr (RESCALE) f = *factor;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t vid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; vid * V < total;
          vid += stride) {
@@ -83,17 +114,21 @@ __global__ void cfg_affine_step_kernel(const T* __restrict__ noise_u,
             const T* xi = reinterpret_cast<const T*>(&xr);
             uint4 orw;
             T* o = reinterpret_cast<T*>(&orw);
-            if constexpr (MASKED) {
+            if constexpr (MASKED || RESCALE) {
                 alignas(16) float iv[V], nv[V], mv[V];
-                load_f32<V>(iv, bl.init + i);
-                load_f32<V>(nv, bl.init_noise + i);
-                load_f32<V>(mv, bl.mask + i % bl.hw);
+                if constexpr (MASKED) {
+                    load_f32<V>(iv, bl.init + i);
+                    load_f32<V>(nv, bl.init_noise + i);
+                    load_f32<V>(mv, bl.mask + i % bl.hw);
+                }
 #pragma unroll
                 for (int j = 0; j < V; ++j) {
                     const float nu = to_f32(u[j]);
-                    const float eps = noise_c ? cfg_eps(nu, to_f32(c[j]), g) : nu;
-                    const float xp = affine_xp<true>(ca, to_f32(xi[j]), cb, eps);
-                    o[j] = from_f32<T>(mask_blend(xp, mv[j], iv[j], nv[j], bl.sa, bl.sb));
+                    float eps = noise_c ? cfg_eps(nu, to_f32(c[j]), g) : nu;
+                    if constexpr (RESCALE) eps = rescale_eps(f, eps);
+                    float xp = affine_xp<true>(ca, to_f32(xi[j]), cb, eps);
+                    if constexpr (MASKED) xp = mask_blend(xp, mv[j], iv[j], nv[j], bl.sa, bl.sb);
+                    o[j] = from_f32<T>(xp);
                 }
             } else {
 #pragma unroll
@@ -104,12 +139,15 @@ __global__ void cfg_affine_step_kernel(const T* __restrict__ noise_u,
                 }
             }
             *reinterpret_cast<uint4*>(out + i) = orw;
-        } else if constexpr (MASKED) {
+        } else if constexpr (MASKED || RESCALE) {
             const float nu = to_f32(noise_u[i]);
-            const float eps = noise_c ? cfg_eps(nu, to_f32(noise_c[i]), g) : nu;
-            const float xp = affine_xp<true>(ca, to_f32(x[i]), cb, eps);
-            out[i] = from_f32<T>(mask_blend(xp, bl.mask[i % bl.hw], bl.init[i], bl.init_noise[i],
-                                            bl.sa, bl.sb));
+            float eps = noise_c ? cfg_eps(nu, to_f32(noise_c[i]), g) : nu;
+            if constexpr (RESCALE) eps = rescale_eps(f, eps);
+            float xp = affine_xp<true>(ca, to_f32(x[i]), cb, eps);
+            if constexpr (MASKED)
+                xp = mask_blend(xp, bl.mask[i % bl.hw], bl.init[i], bl.init_noise[i], bl.sa,
+                                bl.sb);
+            out[i] = from_f32<T>(xp);
         } else {
             const float nu = to_f32(noise_u[i]);
             const float eps = nu + g * (to_f32(noise_c[i]) - nu);
@@ -124,7 +162,7 @@ bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0;
 
 void launch_cfg_affine_step(const void* noise_u, const void* noise_c, const void* x, void* out,
                             float g, float ca, float cb, int64_t total, int dtype,
-                            hipStream_t stream, const MaskBlend* blend) {
+                            hipStream_t stream, const MaskBlend* blend, const float* factor) {
     const int block = 256;
     dispatch_dtype(dtype, [&]<typename T>(std::type_identity<T>) {
         dispatch_bool(blend != nullptr, [&]<bool MASKED>(std::bool_constant<MASKED>) {
@@ -135,10 +173,12 @@ void launch_cfg_affine_step(const void* noise_u, const void* noise_c, const void
                       aligned16(blend->init) && aligned16(blend->init_noise) &&
                       aligned16(blend->mask);
             dispatch_bool(vec, [&]<bool VEC>(std::bool_constant<VEC>) {
-                const int grid = grid_for(total / (VEC ? VecN<T>::value : 1), block);
-                cfg_affine_step_kernel<T, VEC, MASKED><<<grid, block, 0, stream>>>(
-                    (const T*)noise_u, (const T*)noise_c, (const T*)x, (T*)out, g, ca, cb, total,
-                    MASKED ? *blend : MaskBlend{});
+                dispatch_bool(factor != nullptr, [&]<bool RESCALE>(std::bool_constant<RESCALE>) {
+                    const int grid = grid_for(total / (VEC ? VecN<T>::value : 1), block);
+                    cfg_affine_step_kernel<T, VEC, MASKED, RESCALE><<<grid, block, 0, stream>>>(
+                        (const T*)noise_u, (const T*)noise_c, (const T*)x, (T*)out, g, ca, cb,
+                        total, MASKED ? *blend : MaskBlend{}, factor);
+                });
             });
         });
     });
@@ -151,22 +191,28 @@ namespace {
 // x0 state kept in fp32: it reaches ~1/alpha_t * x magnitudes early in the
 // trajectory, where bf16 granularity visibly perturbs the 2M correction.
 // MASKED blends out alone: x0_out is the unmasked kernel's, bit for bit.
-template <typename T, bool MASKED>
+template <typename T, bool MASKED, bool RESCALE>
 __global__ void cfg_dpm_step_kernel(const T* __restrict__ noise_u, const T* __restrict__ noise_c,
                                     const T* __restrict__ x, const float* __restrict__ x0_prev,
                                     T* __restrict__ out, float* __restrict__ x0_out, float g,
                                     float ca, float cb, float cc, float cx, float ce,
-                                    int64_t total, MaskBlend bl) {
+                                    int64_t total, MaskBlend bl,
+                                    const float* __restrict__ factor) {
+    float f = 1.f;
+    if constexpr (RESCALE) f = *factor;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
         const float nu = to_f32(noise_u[i]);
         const float xf = to_f32(x[i]);
-        if constexpr (MASKED) {
-            const float eps = noise_c ? cfg_eps(nu, to_f32(noise_c[i]), g) : nu;
+        if constexpr (MASKED || RESCALE) {
+            float eps = noise_c ? cfg_eps(nu, to_f32(noise_c[i]), g) : nu;
+            if constexpr (RESCALE) eps = rescale_eps(f, eps);
             float prev = affine_xp<sizeof(T) == 2>(ca, xf, cb, eps);
             if (x0_prev) prev = __builtin_fmaf(cc, x0_prev[i], prev);
-            out[i] = from_f32<T>(mask_blend(prev, bl.mask[i % bl.hw], bl.init[i],
-                                            bl.init_noise[i], bl.sa, bl.sb));
+            if constexpr (MASKED)
+                prev = mask_blend(prev, bl.mask[i % bl.hw], bl.init[i], bl.init_noise[i], bl.sa,
+                                  bl.sb);
+            out[i] = from_f32<T>(prev);
             x0_out[i] = affine_xp<false>(cx, xf, ce, eps);
         } else {
             const float eps = nu + g * (to_f32(noise_c[i]) - nu);
@@ -183,16 +229,113 @@ __global__ void cfg_dpm_step_kernel(const T* __restrict__ noise_u, const T* __re
 void launch_cfg_dpm_step(const void* nu, const void* nc, const void* x, const void* x0_prev,
                          void* out, void* x0_out, float g, float ca, float cb, float cc,
                          float cx, float ce, int64_t total, int dtype, hipStream_t stream,
-                         const MaskBlend* blend) {
+                         const MaskBlend* blend, const float* factor) {
     const int block = 256;
     const int grid = grid_for(total, block);
     dispatch_dtype(dtype, [&]<typename T>(std::type_identity<T>) {
         dispatch_bool(blend != nullptr, [&]<bool MASKED>(std::bool_constant<MASKED>) {
-            cfg_dpm_step_kernel<T, MASKED><<<grid, block, 0, stream>>>(
-                (const T*)nu, (const T*)nc, (const T*)x, (const float*)x0_prev, (T*)out,
-                (float*)x0_out, g, ca, cb, cc, cx, ce, total, MASKED ? *blend : MaskBlend{});
+            dispatch_bool(factor != nullptr, [&]<bool RESCALE>(std::bool_constant<RESCALE>) {
+                cfg_dpm_step_kernel<T, MASKED, RESCALE><<<grid, block, 0, stream>>>(
+                    (const T*)nu, (const T*)nc, (const T*)x, (const float*)x0_prev, (T*)out,
+                    (float*)x0_out, g, ca, cb, cc, cx, ce, total, MASKED ? *blend : MaskBlend{},
+                    factor);
+            });
         });
     });
+}
+
+namespace {
+
+// Partial moments of the cond branch and of the CFG result for guidance_rescale.
+// Block b reduces elements [b*CHUNK, min((b+1)*CHUNK, total)) and stores
+// (sum nc, sum nc^2, sum eps, sum eps^2) to ws[b][0..3], fp32. A thread takes
+// groups of V = 16 bytes / sizeof(T) elements, 256 groups apart, with one
+// 16-byte load per branch (VEC: total % V == 0, both pointers 16-byte aligned)
+// or element by element; the groups and the order of the adds are the same, so
+// the two forms give the same bits.
+template <typename T, bool VEC>
+__global__ void __launch_bounds__(CFG_MOMENTS_BLOCK)
+cfg_moments_kernel(const T* __restrict__ noise_u, const T* __restrict__ noise_c, float g,
+                   int64_t total, float* __restrict__ ws) {
+    constexpr int V = VecN<T>::value;
+    __shared__ float lds[2][2 * CFG_MOMENTS_BLOCK / WAVE_SIZE];
+    const int64_t base = (int64_t)blockIdx.x * CFG_MOMENTS_CHUNK;
+    const int64_t end = base + CFG_MOMENTS_CHUNK < total ? base + CFG_MOMENTS_CHUNK : total;
+    float sc = 0.f, qc = 0.f, sg = 0.f, qg = 0.f;
+    for (int64_t i = base + (int64_t)threadIdx.x * V; i < end;
+         i += (int64_t)CFG_MOMENTS_BLOCK * V) {
+        alignas(16) T u[V], c[V];
+        if constexpr (VEC) {
+            *reinterpret_cast<uint4*>(u) = *reinterpret_cast<const uint4*>(noise_u + i);
+            *reinterpret_cast<uint4*>(c) = *reinterpret_cast<const uint4*>(noise_c + i);
+        } else {
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const bool in = i + j < end;
+                u[j] = in ? noise_u[i + j] : from_f32<T>(0.f);
+                c[j] = in ? noise_c[i + j] : from_f32<T>(0.f);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            if (VEC || i + j < end) {
+                const float nc = to_f32(c[j]);
+                const float eps = cfg_eps(to_f32(u[j]), nc, g);
+                sc += nc;
+                qc = __builtin_fmaf(nc, nc, qc);
+                sg += eps;
+                qg = __builtin_fmaf(eps, eps, qg);
+            }
+        }
+    }
+    block_reduce_sum2(sc, qc, lds[0]);
+    block_reduce_sum2(sg, qg, lds[1]);
+    if (threadIdx.x == 0) {
+        float* row = ws + (int64_t)blockIdx.x * 4;
+        row[0] = sc;
+        row[1] = qc;
+        row[2] = sg;
+        row[3] = qg;
+    }
+}
+
+// One wave: lane k < 4 adds column k of ws [nblocks][4] in row order, lane 0
+// forms both variances (n * var = sum x^2 - (sum x)^2 / n; n cancels in the
+// ratio) and stores r = phi * std(nc) / std(eps) + (1 - phi).
+__global__ void cfg_rescale_finalize_kernel(const float* __restrict__ ws, int nblocks,
+                                            float inv_n, float phi, float* __restrict__ factor) {
+    const int lane = threadIdx.x;
+    float acc = 0.f;
+    if (lane < 4)
+        for (int b = 0; b < nblocks; ++b) acc += ws[(int64_t)b * 4 + lane];
+    const float sc = __shfl(acc, 0, WAVE_SIZE), qc = __shfl(acc, 1, WAVE_SIZE);
+    const float sg = __shfl(acc, 2, WAVE_SIZE), qg = __shfl(acc, 3, WAVE_SIZE);
+    if (lane == 0) {
+        const float var_c = fmaxf(qc - sc * sc * inv_n, 0.f);
+        const float var_g = fmaxf(qg - sg * sg * inv_n, 0.f);
+        factor[0] = phi * sqrtf(var_c / var_g) + (1.f - phi);
+    }
+}
+
+}  // namespace
+
+int cfg_moments_blocks(int64_t total) {
+    return (int)((total + CFG_MOMENTS_CHUNK - 1) / CFG_MOMENTS_CHUNK);
+}
+
+void launch_guidance_rescale_factor(const void* noise_u, const void* noise_c, float g, float phi,
+                                    int64_t total, float* ws, float* factor, int dtype,
+                                    hipStream_t stream) {
+    const int nblocks = cfg_moments_blocks(total);
+    dispatch_dtype(dtype, [&]<typename T>(std::type_identity<T>) {
+        const bool vec = total % VecN<T>::value == 0 && aligned16(noise_u) && aligned16(noise_c);
+        dispatch_bool(vec, [&]<bool VEC>(std::bool_constant<VEC>) {
+            cfg_moments_kernel<T, VEC><<<nblocks, CFG_MOMENTS_BLOCK, 0, stream>>>(
+                (const T*)noise_u, (const T*)noise_c, g, total, ws);
+        });
+    });
+    cfg_rescale_finalize_kernel<<<1, WAVE_SIZE, 0, stream>>>(ws, nblocks, 1.0f / (float)total,
+                                                             phi, factor);
 }
 
 namespace {

@@ -17,6 +17,7 @@ from .dispatch import (
     group_norm_apply,
     group_norm_silu,
     group_norm_stats,
+    guidance_rescale_factor,
     hip_ext,
     hip_ext_available,
     inpaint_unet_input,
@@ -43,6 +44,7 @@ __all__ = [
     "group_norm_apply",
     "group_norm_silu",
     "group_norm_stats",
+    "guidance_rescale_factor",
     "hip_ext",
     "hip_ext_available",
     "inpaint_unet_input",

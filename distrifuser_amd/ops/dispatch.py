@@ -291,7 +291,24 @@ def _f32(t: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
     return t.to(device=like.device, dtype=torch.float32)
 
 
-def masked_affine_step(noise, x, init, init_noise, mask, g, ca, cb, sa, sb):
+def guidance_rescale_factor(noise: torch.Tensor, g: float, phi: float) -> torch.Tensor:
+    """fp32 [1]: phi * std(cond) / std(cfg) + (1 - phi) of the [2,C,h,w] CFG
+    pair, cfg = nu + g*(nc - nu), the standard deviations over the one sample
+    (diffusers ``rescale_noise_cfg``). Two launches on GPU with fp32 sums in a
+    fixed order: the same bits on every run. The step ops take the result as
+    their ``factor``."""
+    if use_hip(noise) and noise.dtype in _BOUNDARY_DTYPES:
+        return hip_ext().guidance_rescale_factor(noise, g, phi)
+    return eager.guidance_rescale_factor(noise, g, phi)
+
+
+def _with_factor(factor) -> tuple:
+    """The trailing arguments of a native step: none without a factor, so a
+    plain step makes the call it always made."""
+    return () if factor is None else (factor,)
+
+
+def masked_affine_step(noise, x, init, init_noise, mask, g, ca, cb, sa, sb, factor=None):
     """Inpaint step of DDIM / Euler in one launch on GPU:
 
         eps = nu + g*(nc - nu)   (noise [2,C,h,w]; eps = noise for [1,C,h,w])
@@ -299,23 +316,27 @@ def masked_affine_step(noise, x, init, init_noise, mask, g, ca, cb, sa, sb):
         out = m*x' + (1 - m)*(sa*init + sb*init_noise)
 
     x [1,C,h,w] in bf16, fp16 or fp32; init, init_noise fp32 [1,C,h,w]; mask
-    fp32 with h*w elements, shared by the channels."""
+    fp32 with h*w elements, shared by the channels. factor (from
+    ``guidance_rescale_factor``, CFG pair only) scales eps first."""
     if use_hip(x) and x.dtype in _BOUNDARY_DTYPES:
         return hip_ext().masked_affine_step(noise, x, _f32(init, x), _f32(init_noise, x),
-                                            _f32(mask, x), g, ca, cb, sa, sb)
-    return eager.masked_affine_step(noise, x, init, init_noise, mask, g, ca, cb, sa, sb)
+                                            _f32(mask, x), g, ca, cb, sa, sb,
+                                            *_with_factor(factor))
+    return eager.masked_affine_step(noise, x, init, init_noise, mask, g, ca, cb, sa, sb, factor)
 
 
-def masked_dpm_step(noise, x, x0_prev, init, init_noise, mask, g, ca, cb, cc, cx, ce, sa, sb):
+def masked_dpm_step(noise, x, x0_prev, init, init_noise, mask, g, ca, cb, cc, cx, ce, sa, sb,
+                    factor=None):
     """Inpaint step of DPM-Solver++(2M): cfg_dpm_step with the blend of
-    masked_affine_step on prev. Returns (prev, x0); x0 (fp32) is not blended."""
+    masked_affine_step on prev. Returns (prev, x0); x0 (fp32) is not blended.
+    factor as in masked_affine_step."""
     if use_hip(x) and x.dtype in _BOUNDARY_DTYPES:
         prev, x0 = hip_ext().masked_dpm_step(noise, x, x0_prev, _f32(init, x),
                                              _f32(init_noise, x), _f32(mask, x), g, ca, cb, cc,
-                                             cx, ce, sa, sb)
+                                             cx, ce, sa, sb, *_with_factor(factor))
         return prev, x0
     return eager.masked_dpm_step(noise, x, x0_prev, init, init_noise, mask, g, ca, cb, cc, cx,
-                                 ce, sa, sb)
+                                 ce, sa, sb, factor)
 
 
 def inpaint_unet_input(latents, mask, masked_latents, scale=1.0, copies=1):

@@ -171,14 +171,36 @@ def vae_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.Te
     return torch.einsum("bqk,bkc->bqc", probs, v.float()).to(q.dtype)
 
 
-def _cfg_eps(noise: torch.Tensor, x: torch.Tensor, g: float) -> torch.Tensor:
+def guidance_rescale_factor(noise: torch.Tensor, g: float, phi: float) -> torch.Tensor:
+    """The guidance_rescale factor (diffusers ``rescale_noise_cfg``) of a
+    [2,C,h,w] CFG pair [uncond; cond]:
+
+        cfg = nu + g*(nc - nu),   r = phi * std(nc) / std(cfg) + (1 - phi)
+
+    with both standard deviations over (C, h, w) of the one sample. Computed in
+    float64 from the inputs as given, returned as fp32 [1]: the reference of
+    the kernel pair in csrc/scheduler.hip."""
+    if noise.dim() != 4 or noise.shape[0] != 2:
+        raise ValueError("guidance_rescale_factor: noise must be the [2,C,h,w] CFG pair")
+    nu, nc = noise.double().chunk(2)
+    cfg = nu + g * (nc - nu)
+    r = phi * (nc.std() / cfg.std()) + (1.0 - phi)
+    return r.float().reshape(1)
+
+
+def _cfg_eps(noise: torch.Tensor, x: torch.Tensor, g: float,
+             factor: torch.Tensor | None = None) -> torch.Tensor:
     """fp32 eps of a step: the CFG combine of a [uncond; cond] pair, or the
-    noise itself when it has x's batch (no guidance, g not read)."""
+    noise itself when it has x's batch (no guidance, g not read). factor (one
+    fp32 value, CFG pair only) scales the combined result: guidance_rescale."""
     n = noise.float()
     if n.shape[0] == x.shape[0]:
+        if factor is not None:
+            raise ValueError("a guidance_rescale factor needs the [uncond; cond] noise pair")
         return n
     nu, nc = n.chunk(2)
-    return nu + g * (nc - nu)
+    eps = nu + g * (nc - nu)
+    return eps if factor is None else factor.float().to(eps.device).reshape(()) * eps
 
 
 def _mask_blend(xp, x, init, init_noise, mask, sa, sb):
@@ -189,20 +211,37 @@ def _mask_blend(xp, x, init, init_noise, mask, sa, sb):
     return (m * xp + (1.0 - m) * known).to(x.dtype)
 
 
-def masked_affine_step(noise, x, init, init_noise, mask, g, ca, cb, sa, sb):
+def cfg_affine_step(noise, x, g, ca, cb, factor=None):
+    """x' = ca*x + cb*eps of a CFG pair, eps scaled by factor when given."""
+    return (ca * x.float() + cb * _cfg_eps(noise, x, g, factor)).to(x.dtype)
+
+
+def cfg_dpm_step(noise, x, x0_prev, g, ca, cb, cc, cx, ce, factor=None):
+    """DPM-Solver++(2M) step of a CFG pair -> (prev, x0 fp32); eps scaled by
+    factor when given."""
+    eps = _cfg_eps(noise, x, g, factor)
+    xf = x.float()
+    prev = ca * xf + cb * eps
+    if x0_prev is not None:
+        prev = prev + cc * x0_prev.float()
+    return prev.to(x.dtype), cx * xf + ce * eps
+
+
+def masked_affine_step(noise, x, init, init_noise, mask, g, ca, cb, sa, sb, factor=None):
     """Inpaint step of the affine schedulers (DDIM, Euler): x' = ca*x + cb*eps
     blended with the known region. noise [2,C,h,w] (CFG pair) or [1,C,h,w];
     x [1,C,h,w]; init, init_noise fp32 [1,C,h,w]; mask h*w elements, shared by
-    the channels."""
-    xp = ca * x.float() + cb * _cfg_eps(noise, x, g)
+    the channels. factor: the guidance_rescale factor, CFG pair only."""
+    xp = ca * x.float() + cb * _cfg_eps(noise, x, g, factor)
     return _mask_blend(xp, x, init, init_noise, mask, sa, sb)
 
 
-def masked_dpm_step(noise, x, x0_prev, init, init_noise, mask, g, ca, cb, cc, cx, ce, sa, sb):
+def masked_dpm_step(noise, x, x0_prev, init, init_noise, mask, g, ca, cb, cc, cx, ce, sa, sb,
+                    factor=None):
     """Inpaint step of DPM-Solver++(2M): prev = ca*x + cb*eps (+ cc*x0_prev)
     blended with the known region; x0 = cx*x + ce*eps (fp32) is the unmasked
-    step's. Returns (prev, x0)."""
-    eps = _cfg_eps(noise, x, g)
+    step's. Returns (prev, x0). factor: the guidance_rescale factor."""
+    eps = _cfg_eps(noise, x, g, factor)
     xf = x.float()
     prev = ca * xf + cb * eps
     if x0_prev is not None:

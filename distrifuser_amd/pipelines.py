@@ -62,6 +62,37 @@ def _resolve_tokenizer(pretrained, vocab_size: int, subfolder: str = "tokenizer"
         "allow_simple_tokenizer=True for random-init/debug checkpoints.")
 
 
+_SCHEDULER_FILE_KEYS = ("prediction_type", "timestep_spacing", "rescale_betas_zero_snr",
+                        "beta_start", "beta_end", "steps_offset", "num_train_timesteps")
+_SCHEDULER_KWARGS = _SCHEDULER_FILE_KEYS[:3]
+
+
+def _load_scheduler(name: str, pretrained, kwargs: dict):
+    """The scheduler ``name`` configured from the checkpoint's
+    ``scheduler/scheduler_config.json`` (the keys above, where present) and
+    from ``prediction_type=`` / ``timestep_spacing=`` /
+    ``rescale_betas_zero_snr=`` in ``kwargs`` (popped), which win over the
+    file. A v-prediction checkpoint run as epsilon-prediction gives noise, so
+    the file is read whenever it is there."""
+    config = {}
+    if pretrained is not None:
+        path = os.path.join(pretrained, "scheduler", "scheduler_config.json")
+        if os.path.isfile(path):
+            with open(path, encoding="utf-8") as f:
+                on_file = json.load(f)
+            config = {k: on_file[k] for k in _SCHEDULER_FILE_KEYS if k in on_file}
+    for key in _SCHEDULER_KWARGS:
+        if key in kwargs:
+            config[key] = kwargs.pop(key)
+    return get_scheduler(name, **config)
+
+
+def _check_guidance_rescale(guidance_rescale: float) -> float:
+    if guidance_rescale < 0:
+        raise ValueError(f"guidance_rescale must be >= 0, got {guidance_rescale}")
+    return float(guidance_rescale)
+
+
 def _maybe_tqdm(iterable, enabled: bool):
     if not enabled:
         return iterable
@@ -157,6 +188,12 @@ class _DistriPipelineBase:
                 import shutil
                 shutil.copy(tok.vocab_path, os.path.join(tdir, "vocab.json"))
                 shutil.copy(tok.merges_path, os.path.join(tdir, "merges.txt"))
+        # the prediction type and the schedule travel with the weights
+        sdir = os.path.join(out_dir, "scheduler")
+        os.makedirs(sdir, exist_ok=True)
+        with open(os.path.join(sdir, "scheduler_config.json"), "w", encoding="utf-8") as f:
+            json.dump({"_class_name": type(self.scheduler).__name__, **self.scheduler.config()},
+                      f, indent=2)
 
     @property
     def device(self):
@@ -344,7 +381,8 @@ class _DistriPipelineBase:
         return latents, t_start, inpaint
 
     def _denoise(self, latents, prompt_embeds, added_cond_kwargs, num_inference_steps,
-                 guidance_scale, t_start: int = 0, inpaint: dict | None = None):
+                 guidance_scale, t_start: int = 0, inpaint: dict | None = None,
+                 guidance_rescale: float = 0.0):
         """``t_start > 0`` (img2img) runs the last n - t_start steps only. The
         U-Net counter is 0 at the first step that actually runs, so the
         ``warmup_steps`` synchronous steps of displaced patch parallelism are
@@ -354,9 +392,16 @@ class _DistriPipelineBase:
         ``inpaint`` (from ``_inpaint_latents``) ends every step in the
         scheduler's ``masked_step`` and, with a 9-channel U-Net, assembles the
         U-Net input with ``ops.inpaint_unet_input``. Every rank holds the full
-        latents, so the blend is replicated work like the step itself."""
+        latents, so the blend is replicated work like the step itself.
+
+        ``guidance_rescale`` > 0 goes to the scheduler's ``guided_step`` /
+        ``masked_step`` (the factor op and the fused step with it: three
+        launches on GPU); 0, or classifier-free guidance off, makes the calls
+        made without it."""
         cfg = self.distri_config
         do_cfg = cfg.do_classifier_free_guidance
+        # keyword passed only when set: a plain step is the call it always was
+        rescale = {"guidance_rescale": guidance_rescale} if do_cfg and guidance_rescale > 0 else {}
         from .utils.tracing import trace_range
 
         self.scheduler.set_timesteps(num_inference_steps, device=None)
@@ -381,9 +426,10 @@ class _DistriPipelineBase:
                 if inpaint is not None:
                     latents = self.scheduler.masked_step(
                         noise, t, latents, guidance_scale, inpaint["mask"], inpaint["init"],
-                        inpaint["init_noise"])
+                        inpaint["init_noise"], **rescale)
                 elif do_cfg and hasattr(self.scheduler, "guided_step"):
-                    latents = self.scheduler.guided_step(noise, t, latents, guidance_scale)
+                    latents = self.scheduler.guided_step(noise, t, latents, guidance_scale,
+                                                         **rescale)
                 else:
                     if do_cfg:
                         n_uncond, n_cond = noise.chunk(2)
@@ -392,10 +438,12 @@ class _DistriPipelineBase:
         return latents
 
     def _generate(self, embeds, added_cond_kwargs, num_inference_steps, guidance_scale,
-                  generator, output_type, image, strength, mask=None):
+                  generator, output_type, image, strength, mask=None,
+                  guidance_rescale: float = 0.0):
         """The tail both pipelines share once the prompt is encoded: initial
         (or img2img, or inpaint) latents -> denoise -> decode. ``strength``
         None is 0.3 for img2img and 1.0 for inpainting."""
+        guidance_rescale = _check_guidance_rescale(guidance_rescale)
         if mask is not None and image is None:
             raise ValueError("mask= needs image=: inpainting repaints part of an image")
         if self.unet.config.in_channels == 9 and mask is None:
@@ -411,7 +459,7 @@ class _DistriPipelineBase:
                 image, mask, 1.0 if strength is None else strength, num_inference_steps,
                 generator)
         latents = self._denoise(latents, embeds, added_cond_kwargs, num_inference_steps,
-                                guidance_scale, t_start, inpaint)
+                                guidance_scale, t_start, inpaint, guidance_rescale)
         return self._decode(latents, output_type)
 
     def _decode(self, latents: torch.Tensor, output_type: str):
@@ -536,7 +584,7 @@ class DistriSDXLPipeline(_DistriPipelineBase):
     def from_pretrained(distri_config: DistriConfig, **kwargs):
         pretrained = kwargs.pop("pretrained_model_name_or_path", None)
         torch_dtype = kwargs.pop("torch_dtype", torch.bfloat16)
-        scheduler = kwargs.pop("scheduler", "ddim")
+        scheduler = _load_scheduler(kwargs.pop("scheduler", "ddim"), pretrained, kwargs)
         preset = kwargs.pop("preset", "sdxl")
         allow_simple = kwargs.pop("allow_simple_tokenizer", False)
 
@@ -563,7 +611,7 @@ class DistriSDXLPipeline(_DistriPipelineBase):
             pretrained, {"unet": unet, "vae": vae, "text_encoder": te1, "text_encoder_2": te2},
             distri_config.device, torch_dtype)
         pipeline = DistriSDXLPipeline(distri_config, unet, vae, te1, te2,
-                                      get_scheduler(scheduler), tokenizer,
+                                      scheduler, tokenizer,
                                       tokenizer_2=tokenizer_2)
         pipeline._pretrained_path = pretrained  # for the lazily built VAE encoder
         return pipeline
@@ -621,6 +669,7 @@ class DistriSDXLPipeline(_DistriPipelineBase):
         image=None,
         strength: float | None = None,
         mask=None,
+        guidance_rescale: float = 0.0,
         **kwargs,
     ):
         """Text-to-image, or with ``image=`` img2img (SDEdit): the image (a
@@ -640,7 +689,16 @@ class DistriSDXLPipeline(_DistriPipelineBase):
         so it comes out as encoded. A 9-channel inpaint U-Net (preset
         ``"sdxl-inpaint"``) is also fed the mask and the masked-image
         latents. ``strength`` defaults to 0.3 for img2img and to 1.0, a start
-        from pure noise, with a mask."""
+        from pure noise, with a mask.
+
+        ``guidance_rescale`` (Lin et al., section 3.4; 0.7 is the usual value
+        for v-prediction and zero-terminal-SNR checkpoints) scales the guided
+        model output towards the cond branch's standard deviation before every
+        step. 0 is off; with classifier-free guidance off it is ignored, as
+        in diffusers; a negative value raises ``ValueError``. The prediction
+        type itself belongs to the scheduler: ``from_pretrained(...,
+        prediction_type="v_prediction")`` or the checkpoint's
+        ``scheduler/scheduler_config.json``."""
         assert "height" not in kwargs and "width" not in kwargs, (
             "height/width are fixed by DistriConfig (the comm buffers and "
             "graphs are sized for them)"
@@ -656,7 +714,7 @@ class DistriSDXLPipeline(_DistriPipelineBase):
         pooled = pooled.to(self._unet_dtype())
         added = self._added_cond(embeds.shape[0], pooled)
         return self._generate(embeds, added, num_inference_steps, guidance_scale, generator,
-                              output_type, image, strength, mask)
+                              output_type, image, strength, mask, guidance_rescale)
 
 
 class DistriSDPipeline(_DistriPipelineBase):
@@ -670,7 +728,7 @@ class DistriSDPipeline(_DistriPipelineBase):
     def from_pretrained(distri_config: DistriConfig, **kwargs):
         pretrained = kwargs.pop("pretrained_model_name_or_path", None)
         torch_dtype = kwargs.pop("torch_dtype", torch.bfloat16)
-        scheduler = kwargs.pop("scheduler", "ddim")
+        scheduler = _load_scheduler(kwargs.pop("scheduler", "ddim"), pretrained, kwargs)
         preset = kwargs.pop("preset", "sd15")
         allow_simple = kwargs.pop("allow_simple_tokenizer", False)
 
@@ -706,8 +764,7 @@ class DistriSDPipeline(_DistriPipelineBase):
         unet, vae, te = _DistriPipelineBase._load_components(
             pretrained, {"unet": unet, "vae": vae, "text_encoder": te},
             distri_config.device, torch_dtype)
-        pipeline = DistriSDPipeline(distri_config, unet, vae, te, get_scheduler(scheduler),
-                                    tokenizer)
+        pipeline = DistriSDPipeline(distri_config, unet, vae, te, scheduler, tokenizer)
         pipeline._pretrained_path = pretrained  # for the lazily built VAE encoder
         return pipeline
 
@@ -746,11 +803,13 @@ class DistriSDPipeline(_DistriPipelineBase):
         image=None,
         strength: float | None = None,
         mask=None,
+        guidance_rescale: float = 0.0,
         **kwargs,
     ):
         """Text-to-image, img2img with ``image=`` / ``strength=``, or
-        inpainting with ``mask=`` as well (see ``DistriSDXLPipeline.__call__``;
-        the 9-channel preset here is ``"sd15-inpaint"``)."""
+        inpainting with ``mask=`` as well (see ``DistriSDXLPipeline.__call__``,
+        also for ``guidance_rescale``; the 9-channel preset here is
+        ``"sd15-inpaint"``)."""
         assert "height" not in kwargs and "width" not in kwargs
         cfg = self.distri_config
         if not cfg.do_classifier_free_guidance:
@@ -758,4 +817,4 @@ class DistriSDPipeline(_DistriPipelineBase):
         do_cfg = cfg.do_classifier_free_guidance
         embeds = self.encode_prompt(prompt, negative_prompt, do_cfg).to(self._unet_dtype())
         return self._generate(embeds, None, num_inference_steps, guidance_scale, generator,
-                              output_type, image, strength, mask)
+                              output_type, image, strength, mask, guidance_rescale)

@@ -1,4 +1,4 @@
-"""DDIM (eta=0, epsilon-prediction) — the benchmark-protocol sampler."""
+"""DDIM (eta=0; epsilon- or v-prediction) — the benchmark-protocol sampler."""
 
 from __future__ import annotations
 
@@ -10,35 +10,49 @@ from .common import SchedulerBase
 class DDIMScheduler(SchedulerBase):
     def set_timesteps(self, num_inference_steps: int, device=None) -> None:
         self.num_inference_steps = num_inference_steps
-        self.timesteps = self._leading_timesteps(num_inference_steps)
+        self.timesteps = self._spaced_timesteps(num_inference_steps)
         if device is not None:
             self.timesteps = self.timesteps.to(device)
 
-    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor) -> torch.Tensor:
+    def _alphas(self, timestep):
+        """(acp_t, acp_prev) of the step at ``timestep``, fp32 tensors."""
         t = int(timestep)
         prev_t = t - self.num_train_timesteps // self.num_inference_steps
         acp = self.alphas_cumprod
-        alpha_t = acp[t]
-        alpha_prev = acp[prev_t] if prev_t >= 0 else acp[0]
+        return acp[t], acp[prev_t] if prev_t >= 0 else acp[0]
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor) -> torch.Tensor:
+        alpha_t, alpha_prev = self._alphas(timestep)
 
         x = sample.float()
-        eps = model_output.float()
-        pred_x0 = (x - (1 - alpha_t).sqrt() * eps) / alpha_t.sqrt()
+        if self.v_prediction:
+            v = model_output.float()
+            pred_x0 = alpha_t.sqrt() * x - (1 - alpha_t).sqrt() * v
+            eps = alpha_t.sqrt() * v + (1 - alpha_t).sqrt() * x
+        else:
+            eps = model_output.float()
+            pred_x0 = (x - (1 - alpha_t).sqrt() * eps) / alpha_t.sqrt()
         direction = (1 - alpha_prev).sqrt() * eps
         prev = alpha_prev.sqrt() * pred_x0 + direction
         return prev.to(sample.dtype)
 
     def guided_step(self, noise: torch.Tensor, timestep, sample: torch.Tensor,
-                    guidance_scale: float) -> torch.Tensor:
+                    guidance_scale: float, guidance_rescale: float = 0.0) -> torch.Tensor:
         # CFG combine + DDIM update; noise is the [uncond; cond] pair. On GPU
         # this is ONE fused kernel (csrc/scheduler.hip) - the step math runs
         # outside the captured graphs, so its torch-op launch overhead is
-        # otherwise exposed every denoise step.
+        # otherwise exposed every denoise step. guidance_rescale > 0 adds the
+        # two launches of the factor op in front of it.
         from ..ops import hip_ext, use_hip
 
+        factor = self._rescale_factor(noise, sample, guidance_scale, guidance_rescale)
         if use_hip(noise):
             ca, cb = self._affine_coeffs(timestep)
-            return hip_ext().cfg_affine_step(noise, sample, guidance_scale, ca, cb)
+            if factor is None:
+                return hip_ext().cfg_affine_step(noise, sample, guidance_scale, ca, cb)
+            return hip_ext().cfg_affine_step(noise, sample, guidance_scale, ca, cb, factor)
+        if factor is not None:
+            return self._guided_step_eager(noise, timestep, sample, guidance_scale, factor)
         nu, nc = noise.float().chunk(2)
         eps = nu + guidance_scale * (nc - nu)
         return self.step(eps, timestep, sample)
@@ -46,20 +60,21 @@ class DDIMScheduler(SchedulerBase):
     def _affine_coeffs(self, timestep) -> tuple[float, float]:
         # x' = sqrt(a_p) * (x - sqrt(1-a_t) eps)/sqrt(a_t) + sqrt(1-a_p) eps
         #    = ca * x + cb * eps
-        t = int(timestep)
-        prev_t = t - self.num_train_timesteps // self.num_inference_steps
-        acp = self.alphas_cumprod
-        alpha_t = float(acp[t])
-        alpha_prev = float(acp[prev_t] if prev_t >= 0 else acp[0])
+        alpha_t, alpha_prev = (float(a) for a in self._alphas(timestep))
+        if self.v_prediction:
+            # x' = Ap*(A x - S v) + Sp*(A v + S x): no division by A
+            a, s = alpha_t ** 0.5, (1 - alpha_t) ** 0.5
+            ap, sp = alpha_prev ** 0.5, (1 - alpha_prev) ** 0.5
+            return ap * a + sp * s, sp * a - ap * s
         ca = (alpha_prev / alpha_t) ** 0.5
         cb = (1 - alpha_prev) ** 0.5 - ca * (1 - alpha_t) ** 0.5
         return ca, cb
 
     def _masked_step_native(self, noise, timestep, sample, guidance_scale, mask, init,
-                            init_noise) -> torch.Tensor:
+                            init_noise, factor=None) -> torch.Tensor:
         from ..ops import masked_affine_step
 
         ca, cb = self._affine_coeffs(timestep)
         sa, sb = self._known_coeffs(timestep)
         return masked_affine_step(noise, sample, init, init_noise, mask, guidance_scale, ca, cb,
-                                  sa, sb)
+                                  sa, sb, factor)

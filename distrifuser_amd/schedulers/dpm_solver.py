@@ -1,4 +1,4 @@
-"""DPM-Solver++ (2M, multistep, epsilon-prediction)."""
+"""DPM-Solver++ (2M, multistep; epsilon- or v-prediction)."""
 
 from __future__ import annotations
 
@@ -11,7 +11,7 @@ class DPMSolverMultistepScheduler(SchedulerBase):
     def __init__(self, *args, solver_order: int = 2, **kwargs):
         super().__init__(*args, **kwargs)
         self.solver_order = solver_order
-        acp = self.alphas_cumprod
+        acp = self._finite_alphas_cumprod()
         self.alpha_t = acp.sqrt()
         self.sigma_t = (1 - acp).sqrt()
         self.lambda_t = torch.log(self.alpha_t) - torch.log(self.sigma_t)
@@ -21,7 +21,7 @@ class DPMSolverMultistepScheduler(SchedulerBase):
 
     def set_timesteps(self, num_inference_steps: int, device=None) -> None:
         self.num_inference_steps = num_inference_steps
-        self.timesteps = self._leading_timesteps(num_inference_steps)
+        self.timesteps = self._spaced_timesteps(num_inference_steps)
         if device is not None:
             self.timesteps = self.timesteps.to(device)
         self._x0_prev = None
@@ -47,7 +47,7 @@ class DPMSolverMultistepScheduler(SchedulerBase):
 
         a_t, s_t, l_t = self.alpha_t[t], self.sigma_t[t], self.lambda_t[t]
         a_p, s_p, l_p = self.alpha_t[t_prev], self.sigma_t[t_prev], self.lambda_t[t_prev]
-        x0 = (x - s_t * eps) / a_t
+        x0 = a_t * x - s_t * eps if self.v_prediction else (x - s_t * eps) / a_t
 
         h = l_p - l_t
         if self._x0_prev is None or self.solver_order == 1 or self._step_index == len(self.timesteps) - 1:
@@ -71,24 +71,31 @@ class DPMSolverMultistepScheduler(SchedulerBase):
         return prev.to(sample.dtype)
 
     def guided_step(self, noise: torch.Tensor, timestep, sample: torch.Tensor,
-                    guidance_scale: float) -> torch.Tensor:
+                    guidance_scale: float, guidance_rescale: float = 0.0) -> torch.Tensor:
         """CFG combine + DPM-Solver++(2M) update in ONE fused kernel on GPU.
 
         The 2M update is affine in (x, eps, x0_prev):
             prev = ca*x + cb*eps + cc*x0_prev,   x0 = cx*x + ce*eps
         with C = a_p*(exp(-h)-1), C' = C*(1 + 0.5/r0) (order 2) or C (order 1):
             ca = s_p/s_t - C'/a_t,  cb = C'*s_t/a_t,  cc = 0.5*C/r0.
+        v-prediction changes x0 alone, cx = a_t and ce = -s_t, and with it
+            ca = s_p/s_t - C'*cx,  cb = -C'*ce.
+        guidance_rescale > 0 adds the two launches of the factor op in front.
         """
         from ..ops import hip_ext, use_hip
 
+        factor = self._rescale_factor(noise, sample, guidance_scale, guidance_rescale)
         if not use_hip(noise):
+            if factor is not None:
+                return self._guided_step_eager(noise, timestep, sample, guidance_scale, factor)
             nu, nc = noise.float().chunk(2)
             eps = nu + guidance_scale * (nc - nu)
             return self.step(eps, timestep, sample)
 
         first, coeffs = self._affine_coeffs(timestep)
         prev, x0 = hip_ext().cfg_dpm_step(
-            noise, sample, None if first else self._x0_prev, guidance_scale, *coeffs)
+            noise, sample, None if first else self._x0_prev, guidance_scale, *coeffs,
+            *(() if factor is None else (factor,)))
         self._x0_prev = x0
         self._t_prev = int(timestep)
         self._step_index += 1
@@ -116,6 +123,9 @@ class DPMSolverMultistepScheduler(SchedulerBase):
             r0 = (l_t - l_pp) / h
             cprime = C * (1.0 + 0.5 / r0)
             cc = 0.5 * C / r0
+        if self.v_prediction:
+            cx, ce = a_t, -s_t
+            return first, (s_p / s_t - cprime * cx, -cprime * ce, cc, cx, ce)
         ca = s_p / s_t - cprime / a_t
         cb = cprime * s_t / a_t
         cx = 1.0 / a_t
@@ -123,13 +133,13 @@ class DPMSolverMultistepScheduler(SchedulerBase):
         return first, (ca, cb, cc, cx, ce)
 
     def _masked_step_native(self, noise, timestep, sample, guidance_scale, mask, init,
-                            init_noise) -> torch.Tensor:
+                            init_noise, factor=None) -> torch.Tensor:
         from ..ops import masked_dpm_step
 
         first, coeffs = self._affine_coeffs(timestep)
         sa, sb = self._known_coeffs(timestep)
         prev, x0 = masked_dpm_step(noise, sample, None if first else self._x0_prev, init,
-                                   init_noise, mask, guidance_scale, *coeffs, sa, sb)
+                                   init_noise, mask, guidance_scale, *coeffs, sa, sb, factor)
         self._x0_prev = x0
         self._t_prev = int(timestep)
         self._step_index += 1

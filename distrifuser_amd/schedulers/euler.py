@@ -1,4 +1,4 @@
-"""Euler discrete (epsilon-prediction, leading spacing)."""
+"""Euler discrete (epsilon- or v-prediction)."""
 
 from __future__ import annotations
 
@@ -11,14 +11,14 @@ from .common import SchedulerBase
 class EulerDiscreteScheduler(SchedulerBase):
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
-        acp = self.alphas_cumprod.double()
+        acp = self._finite_alphas_cumprod().double()
         self._sigmas_train = ((1 - acp) / acp).sqrt().numpy()
         self.sigmas: torch.Tensor | None = None
         self._step_index = 0
 
     def set_timesteps(self, num_inference_steps: int, device=None) -> None:
         self.num_inference_steps = num_inference_steps
-        t = self._leading_timesteps(num_inference_steps).numpy().astype(np.float64)
+        t = self._spaced_timesteps(num_inference_steps).numpy().astype(np.float64)
         sigmas = np.interp(t, np.arange(self.num_train_timesteps), self._sigmas_train)
         self.sigmas = torch.tensor(np.concatenate([sigmas, [0.0]]), dtype=torch.float32)
         self.timesteps = torch.tensor(t, dtype=torch.float32)
@@ -48,24 +48,42 @@ class EulerDiscreteScheduler(SchedulerBase):
         sigma_next = self.sigmas[self._step_index + 1].to(sample.device)
         x = sample.float()
         eps = model_output.float()
+        if self.v_prediction:
+            # v is the output for the scaled input x / sqrt(s^2 + 1): the
+            # derivative (x - x0) / s = x * s/(s^2 + 1) + v / sqrt(s^2 + 1)
+            eps = x * (sigma / (sigma**2 + 1)) + eps / (sigma**2 + 1) ** 0.5
         # epsilon prediction: derivative d = eps; x_{t+1} = x + d * (s_next - s)
         prev = x + eps * (sigma_next - sigma)
         self._step_index += 1
         return prev.to(sample.dtype)
 
     def guided_step(self, noise: torch.Tensor, timestep, sample: torch.Tensor,
-                    guidance_scale: float) -> torch.Tensor:
+                    guidance_scale: float, guidance_rescale: float = 0.0) -> torch.Tensor:
         # CFG combine + Euler update in ONE fused kernel on GPU (the update is
-        # affine in (x, eps): ca = 1, cb = sigma_next - sigma)
+        # affine in (x, eps): ca = 1, cb = sigma_next - sigma); guidance_rescale
+        # > 0 adds the two launches of the factor op in front of it
         from ..ops import hip_ext, use_hip
 
+        factor = self._rescale_factor(noise, sample, guidance_scale, guidance_rescale)
         if use_hip(noise):
-            cb = float(self.sigmas[self._step_index + 1] - self.sigmas[self._step_index])
+            ca, cb = self._affine_coeffs()
             self._step_index += 1
-            return hip_ext().cfg_affine_step(noise, sample, guidance_scale, 1.0, cb)
+            if factor is None:
+                return hip_ext().cfg_affine_step(noise, sample, guidance_scale, ca, cb)
+            return hip_ext().cfg_affine_step(noise, sample, guidance_scale, ca, cb, factor)
+        if factor is not None:
+            return self._guided_step_eager(noise, timestep, sample, guidance_scale, factor)
         nu, nc = noise.float().chunk(2)
         eps = nu + guidance_scale * (nc - nu)
         return self.step(eps, timestep, sample)
+
+    def _affine_coeffs(self, timestep=None) -> tuple[float, float]:
+        """(ca, cb) of x' = ca*x + cb*model_output at the current step index."""
+        if not self.v_prediction:
+            return 1.0, float(self.sigmas[self._step_index + 1] - self.sigmas[self._step_index])
+        sigma = float(self.sigmas[self._step_index])
+        dt = float(self.sigmas[self._step_index + 1]) - sigma
+        return 1.0 + dt * sigma / (sigma * sigma + 1.0), dt / (sigma * sigma + 1.0) ** 0.5
 
     # -- inpainting --------------------------------------------------------------
 
@@ -79,11 +97,11 @@ class EulerDiscreteScheduler(SchedulerBase):
         return 1.0, 0.0 if last else float(self.sigmas[self._step_index + 1])
 
     def _masked_step_native(self, noise, timestep, sample, guidance_scale, mask, init,
-                            init_noise) -> torch.Tensor:
+                            init_noise, factor=None) -> torch.Tensor:
         from ..ops import masked_affine_step
 
         sa, sb = self._known_coeffs(timestep)
-        cb = float(self.sigmas[self._step_index + 1] - self.sigmas[self._step_index])
+        ca, cb = self._affine_coeffs()
         self._step_index += 1
-        return masked_affine_step(noise, sample, init, init_noise, mask, guidance_scale, 1.0, cb,
-                                  sa, sb)
+        return masked_affine_step(noise, sample, init, init_noise, mask, guidance_scale, ca, cb,
+                                  sa, sb, factor)

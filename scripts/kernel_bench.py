@@ -2,7 +2,8 @@
 
 Run on an MI355X: python scripts/kernel_bench.py > gpurun_out/kernel_bench.json
 (--splitkv-only: just the split-KV attention sweep; --vae-downsample-only:
-just the VAE-encoder downsample convs; --dtype {bf16,fp16}: the
+just the VAE-encoder downsample convs; --rescale-only: just the rescaled
+DDIM step, native against the torch composition; --dtype {bf16,fp16}: the
 element type of the attention, conv, LayerNorm and VAE-attention rows, default
 bf16 — fp16 rows carry "dtype": "fp16")
 """
@@ -111,6 +112,56 @@ def vae_downsample_rows(results, dt, tag, batches=(1, 25), reps=3):
             print(json.dumps(row), flush=True)
 
 
+def _count_launches(fn):
+    """Device kernels one call of fn launches, from the profiler's trace."""
+    from torch.profiler import ProfilerActivity, profile
+
+    fn()
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    return sum(1 for e in prof.events()
+               if str(e.device_type).endswith("CUDA") and "memcpy" not in e.name.lower())
+
+
+def rescale_step_rows(results, reps=5, iters=200):
+    """One DDIM step with guidance_rescale=0.7 on a bf16 CFG pair, outside any
+    graph: the three native launches (moments, finalize, RESCALE step)
+    against the torch composition of the same maths (chunk, CFG, two std,
+    scale, affine update). Median and range of `reps` timings of `iters`
+    back-to-back calls each."""
+    from distrifuser_amd import ops
+
+    g, phi, ca, cb = 7.5, 0.7, 1.02, -0.05
+    ext = ops.hip_ext()
+    for hw in (128, 480):
+        noise = torch.randn(2, 4, hw, hw, device="cuda:0", dtype=torch.bfloat16)
+        x = torch.randn(1, 4, hw, hw, device="cuda:0", dtype=torch.bfloat16)
+
+        def native():
+            f = ext.guidance_rescale_factor(noise, g, phi)
+            return ext.cfg_affine_step(noise, x, g, ca, cb, f)
+
+        def composed():
+            nu, nc = noise.float().chunk(2)
+            cfg = nu + g * (nc - nu)
+            r = phi * (nc.std() / cfg.std()) + (1 - phi)
+            return (ca * x.float() + cb * (r * cfg)).to(x.dtype)
+
+        err = (native().float() - composed().float()).abs().max().item()
+        row = {"op": "rescaled_ddim_step", "shape": [1, 4, hw, hw], "dtype": "bf16",
+               "max_abs_diff": err,
+               "launches_native": _count_launches(native),
+               "launches_torch": _count_launches(composed)}
+        for name, fn in (("native", native), ("torch", composed)):
+            us = sorted(timeit(fn, iters=iters, warmup=20) * 1000 for _ in range(reps))
+            row[f"us_{name}"] = us[len(us) // 2]
+            row[f"us_{name}_range"] = [us[0], us[-1]]
+        results.append(row)
+        print(json.dumps(row), flush=True)
+
+
 def main():
     assert torch.cuda.is_available()
     from distrifuser_amd import ops
@@ -127,6 +178,10 @@ def main():
         splitkv_sweep(results)
         with open("kernel_bench_splitkv.json", "w") as f:
             json.dump(results, f, indent=1)
+        return 0
+
+    if "--rescale-only" in sys.argv[1:]:
+        rescale_step_rows(results)
         return 0
 
     if "--vae-downsample-only" in sys.argv[1:]:
@@ -212,6 +267,9 @@ def main():
 
     # ---- the VAE encoder's downsample convs (pad_lo=0) ----
     vae_downsample_rows(results, dt, tag)
+
+    # ---- rescaled-CFG DDIM step: three native launches vs the torch ops ----
+    rescale_step_rows(results)
 
     # ---- fused GN+SiLU at SDXL shapes ----
     for c, hw in [(320, 480), (640, 240), (1280, 120), (320, 128), (640, 64)]:

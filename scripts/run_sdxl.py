@@ -33,6 +33,11 @@ def get_args():
     p.add_argument("--guidance_scale", type=float, default=5.0)
     p.add_argument("--scheduler", type=str, default="ddim",
                    choices=["ddim", "euler", "dpm-solver"])
+    p.add_argument("--prediction_type", type=str, default=None,
+                   choices=["epsilon", "v_prediction"],
+                   help="overrides the checkpoint's scheduler_config.json (epsilon without one)")
+    p.add_argument("--guidance_rescale", type=float, default=0.0,
+                   help="rescaled CFG (0.7 for v-prediction / zero-SNR checkpoints); 0 = off")
     p.add_argument("--seed", type=int, default=1234)
     p.add_argument("--pretrained", type=str, default=None,
                    help="local diffusers-layout model dir (random init if omitted)")
@@ -74,9 +79,10 @@ def main():
         use_cuda_graph=not args.no_cuda_graph and torch.cuda.is_available(),
     )
     dtype = torch.bfloat16 if torch.cuda.is_available() else torch.float32
+    sched_kw = {} if args.prediction_type is None else {"prediction_type": args.prediction_type}
     pipe = DistriSDXLPipeline.from_pretrained(
         cfg, torch_dtype=dtype, scheduler=args.scheduler,
-        pretrained_model_name_or_path=args.pretrained, preset=args.preset,
+        pretrained_model_name_or_path=args.pretrained, preset=args.preset, **sched_kw,
     )
     if args.tile_decode:
         pipe.vae.enable_tiling()
@@ -88,6 +94,7 @@ def main():
             generator=g,
             num_inference_steps=args.num_inference_steps,
             guidance_scale=args.guidance_scale,
+            guidance_rescale=args.guidance_rescale,
             output_type=output_type,
         )
 

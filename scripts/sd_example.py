@@ -1,4 +1,7 @@
-"""Minimal SD1.5 usage example (parity with the reference's sd_example.py)."""
+"""Minimal SD1.5 usage example (parity with the reference's sd_example.py).
+
+--prediction_type v_prediction --guidance_rescale 0.7 is the setting of the
+SD 2.x 768 checkpoints."""
 
 import os
 import sys
@@ -6,20 +9,29 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+import argparse
+
 import torch
 
 from distrifuser_amd import DistriConfig, DistriSDPipeline
+
+parser = argparse.ArgumentParser()
+parser.add_argument("--prediction_type", default="epsilon", choices=["epsilon", "v_prediction"])
+parser.add_argument("--guidance_rescale", type=float, default=0.0)
+args = parser.parse_args()
 
 distri_config = DistriConfig(height=512, width=512, mode="stale_gn")
 pipeline = DistriSDPipeline.from_pretrained(
     distri_config,
     torch_dtype=torch.bfloat16 if torch.cuda.is_available() else torch.float32,
+    prediction_type=args.prediction_type,
 )
 
 pipeline.set_progress_bar_config(disable=distri_config.rank != 0)
 image = pipeline(
     prompt="A kitten sitting in a teacup, studio lighting",
     generator=torch.Generator().manual_seed(233),
+    guidance_rescale=args.guidance_rescale,
     output_type="pil",
 )
 if distri_config.rank == 0:
