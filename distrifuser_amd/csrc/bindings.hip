@@ -4,6 +4,7 @@
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
 
 #include <array>
@@ -219,21 +220,61 @@ at::Tensor guidance_rescale_factor(const at::Tensor& noise, double g, double phi
     return factor;
 }
 
+// noise=(cn, seed, draw) of a stochastic step, or nothing: x' += cn * z with z
+// the Philox normal of (seed, draw, element index). The index is the element's
+// offset in the one sample, so x must be [1,C,h,w].
+using NoiseArg = std::optional<std::tuple<double, uint64_t, uint32_t>>;
+struct StepNoiseArg {
+    StepNoise value;
+    bool given;
+    const StepNoise* ptr() const { return given ? &value : nullptr; }
+};
+StepNoiseArg step_noise(const char* op, const NoiseArg& noise, const at::Tensor& x) {
+    if (!noise.has_value()) return {{0.f, 0, 0}, false};
+    TORCH_CHECK(x.dim() == 4 && x.size(0) == 1, op,
+                ": a noisy step needs x [1,C,h,w] (one sample)");
+    return {{(float)std::get<0>(*noise), std::get<1>(*noise), std::get<2>(*noise)}, true};
+}
+
+// The unmasked step ops take the [2,C,h,w] CFG pair, or with noise= also the
+// single-branch output in x's shape; -> the cond half, null without a pair
+const void* cond_half(const char* op, const at::Tensor& n, const at::Tensor& xc, bool noisy) {
+    TORCH_CHECK(n.is_cuda() && xc.is_cuda() && n.scalar_type() == xc.scalar_type(), op,
+                ": noise and x must be CUDA tensors of one dtype");
+    if (noisy && n.numel() == xc.numel()) return nullptr;
+    TORCH_CHECK(n.size(0) == 2 && xc.numel() * 2 == n.numel(), op,
+                ": noise must be the [2,C,h,w] CFG pair",
+                noisy ? " or, with noise=, the output [1,C,h,w] of one branch" : "");
+    return reinterpret_cast<const char*>(n.data_ptr()) + xc.numel() * n.element_size();
+}
+
 at::Tensor cfg_affine_step(const at::Tensor& noise, const at::Tensor& x, double g, double ca,
-                           double cb, const c10::optional<at::Tensor>& factor) {
+                           double cb, const c10::optional<at::Tensor>& factor,
+                           const NoiseArg& znoise) {
     // noise: [2, C, H, W] = [uncond; cond]; x: [1, C, H, W]; out = ca*x + cb*eps
-    TORCH_CHECK(noise.is_cuda() && noise.size(0) == 2);
+    TORCH_CHECK(noise.is_cuda() && noise.dim() >= 1);
     auto n = noise.contiguous();
     auto xc = x.contiguous();
-    TORCH_CHECK(xc.numel() * 2 == n.numel());
+    const auto nz = step_noise("cfg_affine_step", znoise, x);
+    const void* nc = cond_half("cfg_affine_step", n, xc, nz.given);
     const float* fp = rescale_factor("cfg_affine_step", factor, noise, x);
     auto out = at::empty_like(xc);
-    const int64_t total = xc.numel();
-    launch_cfg_affine_step(
-        n.data_ptr(),
-        reinterpret_cast<const char*>(n.data_ptr()) + total * n.element_size(), xc.data_ptr(),
-        out.data_ptr(), (float)g, (float)ca, (float)cb, total, dtype_of(xc), cur_stream(),
-        nullptr, fp);
+    launch_cfg_affine_step(n.data_ptr(), nc, xc.data_ptr(), out.data_ptr(), (float)g, (float)ca,
+                           (float)cb, xc.numel(), dtype_of(xc), cur_stream(), nullptr, fp,
+                           nz.ptr());
+    return out;
+}
+
+// fp32 [numel]: the normals of elements offset .. offset + numel - 1 of the
+// stream (seed, draw), csrc/philox.h
+at::Tensor philox_normal(int64_t numel, uint64_t seed, uint32_t draw, int64_t offset,
+                         int64_t device_index) {
+    TORCH_CHECK(numel >= 0 && offset >= 0 && offset <= INT64_MAX - numel,
+                "philox_normal: numel and offset must be >= 0 and their sum an int64");
+    const c10::Device device(c10::kCUDA, (c10::DeviceIndex)device_index);
+    const c10::DeviceGuard guard(device);  // the launch and its stream are that device's
+    auto out = at::empty({numel}, at::TensorOptions().dtype(at::kFloat).device(device));
+    launch_philox_normal(out.data_ptr<float>(), numel, offset, seed, draw, cur_stream());
     return out;
 }
 
@@ -274,13 +315,15 @@ MaskedStepArgs masked_step_args(const char* op, const at::Tensor& noise, const a
 at::Tensor masked_affine_step(const at::Tensor& noise, const at::Tensor& x,
                               const at::Tensor& init, const at::Tensor& init_noise,
                               const at::Tensor& mask, double g, double ca, double cb, double sa,
-                              double sb, const c10::optional<at::Tensor>& factor) {
+                              double sb, const c10::optional<at::Tensor>& factor,
+                              const NoiseArg& znoise) {
     auto a = masked_step_args("masked_affine_step", noise, x, init, init_noise, mask, sa, sb);
     const float* fp = rescale_factor("masked_affine_step", factor, noise, x);
+    const auto nz = step_noise("masked_affine_step", znoise, x);
     auto out = at::empty_like(a.x);
     launch_cfg_affine_step(a.n.data_ptr(), a.nc, a.x.data_ptr(), out.data_ptr(), (float)g,
                            (float)ca, (float)cb, a.x.numel(), dtype_of(a.x), cur_stream(),
-                           &a.blend, fp);
+                           &a.blend, fp, nz.ptr());
     return out;
 }
 
@@ -584,7 +627,8 @@ at::Tensor conv3x3(const at::Tensor& x, const at::Tensor& wp,
 std::vector<at::Tensor> dpm_step(const at::Tensor& n, const void* nc, const at::Tensor& xc,
                                  const c10::optional<at::Tensor>& x0_prev, double g, double ca,
                                  double cb, double cc, double cx, double ce,
-                                 const MaskBlend* blend, const float* factor) {
+                                 const MaskBlend* blend, const float* factor,
+                                 const StepNoise* noise) {
     const void* pp = nullptr;
     at::Tensor p;
     if (x0_prev.has_value()) {
@@ -597,22 +641,22 @@ std::vector<at::Tensor> dpm_step(const at::Tensor& n, const void* nc, const at::
     auto x0 = at::empty_like(xc, xc.options().dtype(at::kFloat));
     launch_cfg_dpm_step(n.data_ptr(), nc, xc.data_ptr(), pp, out.data_ptr(), x0.data_ptr(),
                         (float)g, (float)ca, (float)cb, (float)cc, (float)cx, (float)ce,
-                        xc.numel(), dtype_of(xc), cur_stream(), blend, factor);
+                        xc.numel(), dtype_of(xc), cur_stream(), blend, factor, noise);
     return {out, x0};
 }
 
 std::vector<at::Tensor> cfg_dpm_step(const at::Tensor& noise, const at::Tensor& x,
                                      const c10::optional<at::Tensor>& x0_prev, double g,
                                      double ca, double cb, double cc, double cx, double ce,
-                                     const c10::optional<at::Tensor>& factor) {
-    TORCH_CHECK(noise.is_cuda() && noise.size(0) == 2);
+                                     const c10::optional<at::Tensor>& factor,
+                                     const NoiseArg& znoise) {
+    TORCH_CHECK(noise.is_cuda() && noise.dim() >= 1);
     auto n = noise.contiguous();
     auto xc = x.contiguous();
-    TORCH_CHECK(xc.numel() * 2 == n.numel());
-    const void* nc =
-        reinterpret_cast<const char*>(n.data_ptr()) + xc.numel() * n.element_size();
+    const auto nz = step_noise("cfg_dpm_step", znoise, x);
+    const void* nc = cond_half("cfg_dpm_step", n, xc, nz.given);
     return dpm_step(n, nc, xc, x0_prev, g, ca, cb, cc, cx, ce, nullptr,
-                    rescale_factor("cfg_dpm_step", factor, noise, x));
+                    rescale_factor("cfg_dpm_step", factor, noise, x), nz.ptr());
 }
 
 // cfg_dpm_step with the inpaint blend on prev; x0 is the unmasked step's
@@ -621,10 +665,12 @@ std::vector<at::Tensor> masked_dpm_step(const at::Tensor& noise, const at::Tenso
                                         const at::Tensor& init, const at::Tensor& init_noise,
                                         const at::Tensor& mask, double g, double ca, double cb,
                                         double cc, double cx, double ce, double sa, double sb,
-                                        const c10::optional<at::Tensor>& factor) {
+                                        const c10::optional<at::Tensor>& factor,
+                                        const NoiseArg& znoise) {
     auto a = masked_step_args("masked_dpm_step", noise, x, init, init_noise, mask, sa, sb);
+    const auto nz = step_noise("masked_dpm_step", znoise, x);
     return dpm_step(a.n, a.nc, a.x, x0_prev, g, ca, cb, cc, cx, ce, &a.blend,
-                    rescale_factor("masked_dpm_step", factor, noise, x));
+                    rescale_factor("masked_dpm_step", factor, noise, x), nz.ptr());
 }
 
 at::Tensor layer_norm(const at::Tensor& x_, const at::Tensor& w_, const at::Tensor& b_,
@@ -723,7 +769,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("cfg_affine_step", &cfg_affine_step,
           "fused CFG combine + affine scheduler update; factor: the guidance_rescale factor",
           pybind11::arg("noise"), pybind11::arg("x"), pybind11::arg("g"), pybind11::arg("ca"),
-          pybind11::arg("cb"), pybind11::arg("factor") = pybind11::none());
+          pybind11::arg("cb"), pybind11::arg("factor") = pybind11::none(),
+          pybind11::arg("step_noise") = pybind11::none());
+    m.def("philox_normal", &philox_normal,
+          "Philox4x32-10 Box-Muller normals of elements offset.. of (seed, draw) -> fp32 [numel]",
+          pybind11::arg("numel"), pybind11::arg("seed"), pybind11::arg("draw"),
+          pybind11::arg("offset") = 0, pybind11::arg("device_index") = 0);
     m.def("flash_attention", &flash_attention, "bf16/fp16 flash attention (chunked stale KV)");
     m.def("flash_attention_ext", &flash_attention_ext,
           "flash attention with split-KV and optional log-sum-exp -> [out] or [out, lse]",
@@ -738,20 +789,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("cfg_dpm_step", &cfg_dpm_step, "fused CFG + DPM-Solver++(2M) update -> (prev, x0)",
           pybind11::arg("noise"), pybind11::arg("x"), pybind11::arg("x0_prev"),
           pybind11::arg("g"), pybind11::arg("ca"), pybind11::arg("cb"), pybind11::arg("cc"),
-          pybind11::arg("cx"), pybind11::arg("ce"), pybind11::arg("factor") = pybind11::none());
+          pybind11::arg("cx"), pybind11::arg("ce"), pybind11::arg("factor") = pybind11::none(),
+          pybind11::arg("step_noise") = pybind11::none());
     m.def("masked_affine_step", &masked_affine_step,
           "inpaint: (CFG +) affine scheduler update blended with the re-noised init latents",
           pybind11::arg("noise"), pybind11::arg("x"), pybind11::arg("init"),
           pybind11::arg("init_noise"), pybind11::arg("mask"), pybind11::arg("g"),
           pybind11::arg("ca"), pybind11::arg("cb"), pybind11::arg("sa"), pybind11::arg("sb"),
-          pybind11::arg("factor") = pybind11::none());
+          pybind11::arg("factor") = pybind11::none(), pybind11::arg("step_noise") = pybind11::none());
     m.def("masked_dpm_step", &masked_dpm_step,
           "inpaint: (CFG +) DPM-Solver++(2M) update, prev blended -> (prev, x0)",
           pybind11::arg("noise"), pybind11::arg("x"), pybind11::arg("x0_prev"),
           pybind11::arg("init"), pybind11::arg("init_noise"), pybind11::arg("mask"),
           pybind11::arg("g"), pybind11::arg("ca"), pybind11::arg("cb"), pybind11::arg("cc"),
           pybind11::arg("cx"), pybind11::arg("ce"), pybind11::arg("sa"), pybind11::arg("sb"),
-          pybind11::arg("factor") = pybind11::none());
+          pybind11::arg("factor") = pybind11::none(), pybind11::arg("step_noise") = pybind11::none());
     m.def("inpaint_unet_input", &inpaint_unet_input,
           "inpaint U-Net input [copies,9,h,w] = [latents / scale, mask, masked-image latents]");
     m.def("layer_norm", &layer_norm, "bf16/fp16 fused LayerNorm");

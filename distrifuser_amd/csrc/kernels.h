@@ -70,6 +70,18 @@ struct MaskBlend {
     int64_t hw;
 };
 
+// ---- the noise term of a stochastic scheduler step ----------------------------
+// x' += cn * z, z the Philox normal of (seed, draw, element index): philox.h.
+struct StepNoise {
+    float cn;
+    uint64_t seed;
+    uint32_t draw;
+};
+
+// out[e] = the normal of element offset + e, e in [0, numel): fp32
+void launch_philox_normal(float* out, int64_t numel, int64_t offset, uint64_t seed,
+                          uint32_t draw, hipStream_t stream);
+
 // ---- guidance_rescale factor ---------------------------------------------------
 // factor[0] = phi * std(nc) / std(eps) + (1 - phi), eps = nu + g*(nc - nu), both
 // standard deviations over the `total` elements of the one sample; fp32 sums.
@@ -89,10 +101,14 @@ void launch_guidance_rescale_factor(const void* noise_u, const void* noise_c, fl
 // factor != null (one fp32 on the device, noise_c not null): eps is replaced
 // by round(factor[0] * eps) before the update. A factor of 1 gives the bits
 // of the call without one.
+// noise != null with cn != 0: out = fma(cn, z, x') before any blend, z indexed
+// by the element's offset in the one sample; noise_c may then be null as well.
+// cn == 0 runs the instantiation of the call without noise, except for the
+// call that has none (no pair, no blend), which then adds 0 * z.
 void launch_cfg_affine_step(const void* noise_u, const void* noise_c, const void* x, void* out,
                             float g, float ca, float cb, int64_t total, int dtype,
                             hipStream_t stream, const MaskBlend* blend = nullptr,
-                            const float* factor = nullptr);
+                            const float* factor = nullptr, const StepNoise* noise = nullptr);
 
 // ---- inpaint U-Net input assembly --------------------------------------------
 // out [copies, 9, hw]: channels 0..3 = latents [4, hw] / scale, channel 4 =
@@ -136,10 +152,13 @@ void launch_conv3x3(const Conv3x3Params& p, int stride, int dtype, hipStream_t s
 // out = ca*x + cb*eps + cc*x0_prev (x0_prev may be null); x0_out = cx*x + ce*eps
 // blend != null: out is blended as in the masked affine step (nc may be null);
 // x0_out is not. factor as in the affine step: out and x0_out both use eps_r.
+// noise as in the affine step: added to out after the x0_prev term and before
+// the blend; x0_out never sees it.
 void launch_cfg_dpm_step(const void* nu, const void* nc, const void* x, const void* x0_prev,
                          void* out, void* x0_out, float g, float ca, float cb, float cc,
                          float cx, float ce, int64_t total, int dtype, hipStream_t stream,
-                         const MaskBlend* blend = nullptr, const float* factor = nullptr);
+                         const MaskBlend* blend = nullptr, const float* factor = nullptr,
+                         const StepNoise* noise = nullptr);
 
 // ---- fused (residual +) LayerNorm (bf16 or fp16, C <= 2048, C % 8 == 0) -------------
 // y = LN(x [+ res]); when res != null and sum_out != null, x+res is also

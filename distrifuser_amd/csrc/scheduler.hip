@@ -36,8 +36,25 @@
 // workspace row, cfg_rescale_finalize_kernel adds the rows in index order.
 // No atomics, and a block count that depends on the element count alone: the
 // factor is the same bits on every run and every device.
+//
+// The stochastic samplers (the NOISE axis of both step kernels) add one term
+// to the same affine step, before any blend:
+//
+//   x' = fma(cn, z, x')                    z ~ N(0, 1)
+//
+// Euler ancestral: cn = sigma_up; DDIM with eta > 0: cn = the DDIM sigma;
+// DPM-Solver++ SDE: cn = s_p * sqrt(1 - e^-2h). z is the Philox4x32-10 normal
+// of (seed, draw, the element's index in the sample), philox.h: the same bits
+// for every element type, for the 16-byte and the element-wise path and for
+// every launch geometry. A vector thread computes whole Philox blocks (two for
+// eight 16-bit elements, one for four fp32), the element-wise paths one block
+// per element, of which they take their lane. Like MASKED, a NOISE step runs
+// without a CFG pair (noise_c null: eps = nu). cn == 0 takes NOISE = false:
+// every deterministic step runs the instantiation it ran before the axis
+// existed.
 
 #include "dispatch.h"
+#include "philox.h"
 
 // elements per block of cfg_moments_kernel, a constant of the arithmetic (it
 // fixes the summation tree): 8 blocks at 1024^2, 113 at 3840^2
@@ -82,22 +99,36 @@ __device__ __forceinline__ float rescale_eps(float f, float eps) {
     return r;
 }
 
+// x' of a NOISE step, fma(cn, z, x') rounded to fp32. The empty asm keeps the
+// value in a register as it is: without it the compiler folds this fma and the
+// conversion to fp16 that follows into one v_fma_mixlo_f16, which rounds the
+// exact sum straight to fp16, while a masked step (the blend comes between)
+// rounds to fp32 first; m == 1 would then miss the unmasked step by one fp16
+// ulp near a tie. Rounded to fp32 first, as the eager reference does.
+__device__ __forceinline__ float add_step_noise(float cn, float z, float xp) {
+    float r = __builtin_fmaf(cn, z, xp);
+    asm volatile("" : "+v"(r));
+    return r;
+}
+
 __device__ __forceinline__ float mask_blend(float xp, float m, float init, float init_noise,
                                             float sa, float sb) {
     const float known = sa * init + sb * init_noise;
     return m * xp + (1.f - m) * known;
 }
 
-// VEC && MASKED: hw % V == 0, so a vector never straddles a plane. MASKED and
-// RESCALE share the explicitly rounded form; RESCALE reads *factor, noise_c is
-// then never null.
-template <typename T, bool VEC, bool MASKED, bool RESCALE>
+// VEC && MASKED: hw % V == 0, so a vector never straddles a plane. MASKED,
+// RESCALE and NOISE share the explicitly rounded form; RESCALE reads *factor,
+// noise_c is then never null. NOISE: element i of the sample draws z(i).
+template <typename T, bool VEC, bool MASKED, bool RESCALE, bool NOISE>
 __global__ void cfg_affine_step_kernel(const T* __restrict__ noise_u,
                                        const T* __restrict__ noise_c, const T* __restrict__ x,
                                        T* __restrict__ out, float g, float ca, float cb,
                                        int64_t total, MaskBlend bl,
-                                       const float* __restrict__ factor) {
+                                       const float* __restrict__ factor, float cn,
+                                       PhiloxKey key) {
     constexpr int V = VEC ? VecN<T>::value : 1;
+    constexpr bool EXPLICIT = MASKED || RESCALE || NOISE;
     float f = 1.f;
     if constexpr (RESCALE) f = *factor;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -107,19 +138,25 @@ __global__ void cfg_affine_step_kernel(const T* __restrict__ noise_u,
         if (VEC) {
             uint4 ur = *reinterpret_cast<const uint4*>(noise_u + i);
             uint4 cr = ur;
-            if (!MASKED || noise_c) cr = *reinterpret_cast<const uint4*>(noise_c + i);
+            if (!(MASKED || NOISE) || noise_c) cr = *reinterpret_cast<const uint4*>(noise_c + i);
             uint4 xr = *reinterpret_cast<const uint4*>(x + i);
             const T* u = reinterpret_cast<const T*>(&ur);
             const T* c = reinterpret_cast<const T*>(&cr);
             const T* xi = reinterpret_cast<const T*>(&xr);
             uint4 orw;
             T* o = reinterpret_cast<T*>(&orw);
-            if constexpr (MASKED || RESCALE) {
+            if constexpr (EXPLICIT) {
                 alignas(16) float iv[V], nv[V], mv[V];
                 if constexpr (MASKED) {
                     load_f32<V>(iv, bl.init + i);
                     load_f32<V>(nv, bl.init_noise + i);
                     load_f32<V>(mv, bl.mask + i % bl.hw);
+                }
+                float zv[(V + 3) / 4][4];  // i % 4 == 0: whole blocks
+                if constexpr (NOISE) {
+#pragma unroll
+                    for (int b = 0; b < V / 4; ++b)
+                        philox_normal4(key, (uint64_t)(i >> 2) + b, zv[b]);
                 }
 #pragma unroll
                 for (int j = 0; j < V; ++j) {
@@ -127,6 +164,7 @@ __global__ void cfg_affine_step_kernel(const T* __restrict__ noise_u,
                     float eps = noise_c ? cfg_eps(nu, to_f32(c[j]), g) : nu;
                     if constexpr (RESCALE) eps = rescale_eps(f, eps);
                     float xp = affine_xp<true>(ca, to_f32(xi[j]), cb, eps);
+                    if constexpr (NOISE) xp = add_step_noise(cn, zv[j / 4][j % 4], xp);
                     if constexpr (MASKED) xp = mask_blend(xp, mv[j], iv[j], nv[j], bl.sa, bl.sb);
                     o[j] = from_f32<T>(xp);
                 }
@@ -139,11 +177,12 @@ __global__ void cfg_affine_step_kernel(const T* __restrict__ noise_u,
                 }
             }
             *reinterpret_cast<uint4*>(out + i) = orw;
-        } else if constexpr (MASKED || RESCALE) {
+        } else if constexpr (EXPLICIT) {
             const float nu = to_f32(noise_u[i]);
             float eps = noise_c ? cfg_eps(nu, to_f32(noise_c[i]), g) : nu;
             if constexpr (RESCALE) eps = rescale_eps(f, eps);
             float xp = affine_xp<true>(ca, to_f32(x[i]), cb, eps);
+            if constexpr (NOISE) xp = add_step_noise(cn, philox_normal1(key, (uint64_t)i), xp);
             if constexpr (MASKED)
                 xp = mask_blend(xp, bl.mask[i % bl.hw], bl.init[i], bl.init_noise[i], bl.sa,
                                 bl.sb);
@@ -158,15 +197,34 @@ __global__ void cfg_affine_step_kernel(const T* __restrict__ noise_u,
 
 bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
+// Whether a step takes its NOISE instantiation: cn != 0, or the one call that
+// has no instantiation without it (no CFG pair and no blend: the plain kernels
+// always read noise_c), which then adds 0 * z.
+bool step_draws(const StepNoise* noise, const void* noise_c, const MaskBlend* blend) {
+    return noise != nullptr && (noise->cn != 0.f || (noise_c == nullptr && blend == nullptr));
+}
+
+PhiloxKey philox_key(const StepNoise* noise) {
+    if (noise == nullptr) return PhiloxKey{0u, 0u, 0u};
+    return PhiloxKey{(uint32_t)noise->seed, (uint32_t)(noise->seed >> 32), noise->draw};
+}
+
 }  // namespace
 
 void launch_cfg_affine_step(const void* noise_u, const void* noise_c, const void* x, void* out,
                             float g, float ca, float cb, int64_t total, int dtype,
-                            hipStream_t stream, const MaskBlend* blend, const float* factor) {
+                            hipStream_t stream, const MaskBlend* blend, const float* factor,
+                            const StepNoise* noise) {
     const int block = 256;
+    const bool noisy = step_draws(noise, noise_c, blend);
+    const float cn = noisy ? noise->cn : 0.f;
+    const PhiloxKey key = philox_key(noisy ? noise : nullptr);
     dispatch_dtype(dtype, [&]<typename T>(std::type_identity<T>) {
         dispatch_bool(blend != nullptr, [&]<bool MASKED>(std::bool_constant<MASKED>) {
             bool vec = total % VecN<T>::value == 0;
+            if (noisy)  // noise_c may be null: aligned16(nullptr) holds
+                vec = vec && aligned16(noise_u) && aligned16(noise_c) && aligned16(x) &&
+                      aligned16(out);
             if constexpr (MASKED)
                 vec = blend->hw % VecN<T>::value == 0 && aligned16(noise_u) &&
                       aligned16(noise_c) && aligned16(x) && aligned16(out) &&
@@ -174,10 +232,13 @@ void launch_cfg_affine_step(const void* noise_u, const void* noise_c, const void
                       aligned16(blend->mask);
             dispatch_bool(vec, [&]<bool VEC>(std::bool_constant<VEC>) {
                 dispatch_bool(factor != nullptr, [&]<bool RESCALE>(std::bool_constant<RESCALE>) {
-                    const int grid = grid_for(total / (VEC ? VecN<T>::value : 1), block);
-                    cfg_affine_step_kernel<T, VEC, MASKED, RESCALE><<<grid, block, 0, stream>>>(
-                        (const T*)noise_u, (const T*)noise_c, (const T*)x, (T*)out, g, ca, cb,
-                        total, MASKED ? *blend : MaskBlend{}, factor);
+                    dispatch_bool(noisy, [&]<bool NOISE>(std::bool_constant<NOISE>) {
+                        const int grid = grid_for(total / (VEC ? VecN<T>::value : 1), block);
+                        cfg_affine_step_kernel<T, VEC, MASKED, RESCALE, NOISE>
+                            <<<grid, block, 0, stream>>>(
+                                (const T*)noise_u, (const T*)noise_c, (const T*)x, (T*)out, g, ca,
+                                cb, total, MASKED ? *blend : MaskBlend{}, factor, cn, key);
+                    });
                 });
             });
         });
@@ -191,24 +252,27 @@ namespace {
 // x0 state kept in fp32: it reaches ~1/alpha_t * x magnitudes early in the
 // trajectory, where bf16 granularity visibly perturbs the 2M correction.
 // MASKED blends out alone: x0_out is the unmasked kernel's, bit for bit.
-template <typename T, bool MASKED, bool RESCALE>
+// NOISE: prev += cn * z(i) after the x0_prev term and before the blend; x0_out
+// is the noise-free call's, bit for bit.
+template <typename T, bool MASKED, bool RESCALE, bool NOISE>
 __global__ void cfg_dpm_step_kernel(const T* __restrict__ noise_u, const T* __restrict__ noise_c,
                                     const T* __restrict__ x, const float* __restrict__ x0_prev,
                                     T* __restrict__ out, float* __restrict__ x0_out, float g,
                                     float ca, float cb, float cc, float cx, float ce,
                                     int64_t total, MaskBlend bl,
-                                    const float* __restrict__ factor) {
+                                    const float* __restrict__ factor, float cn, PhiloxKey key) {
     float f = 1.f;
     if constexpr (RESCALE) f = *factor;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
         const float nu = to_f32(noise_u[i]);
         const float xf = to_f32(x[i]);
-        if constexpr (MASKED || RESCALE) {
+        if constexpr (MASKED || RESCALE || NOISE) {
             float eps = noise_c ? cfg_eps(nu, to_f32(noise_c[i]), g) : nu;
             if constexpr (RESCALE) eps = rescale_eps(f, eps);
             float prev = affine_xp<sizeof(T) == 2>(ca, xf, cb, eps);
             if (x0_prev) prev = __builtin_fmaf(cc, x0_prev[i], prev);
+            if constexpr (NOISE) prev = add_step_noise(cn, philox_normal1(key, (uint64_t)i), prev);
             if constexpr (MASKED)
                 prev = mask_blend(prev, bl.mask[i % bl.hw], bl.init[i], bl.init_noise[i], bl.sa,
                                   bl.sb);
@@ -229,19 +293,55 @@ __global__ void cfg_dpm_step_kernel(const T* __restrict__ noise_u, const T* __re
 void launch_cfg_dpm_step(const void* nu, const void* nc, const void* x, const void* x0_prev,
                          void* out, void* x0_out, float g, float ca, float cb, float cc,
                          float cx, float ce, int64_t total, int dtype, hipStream_t stream,
-                         const MaskBlend* blend, const float* factor) {
+                         const MaskBlend* blend, const float* factor, const StepNoise* noise) {
     const int block = 256;
     const int grid = grid_for(total, block);
+    const bool noisy = step_draws(noise, nc, blend);
+    const float cn = noisy ? noise->cn : 0.f;
+    const PhiloxKey key = philox_key(noisy ? noise : nullptr);
     dispatch_dtype(dtype, [&]<typename T>(std::type_identity<T>) {
         dispatch_bool(blend != nullptr, [&]<bool MASKED>(std::bool_constant<MASKED>) {
             dispatch_bool(factor != nullptr, [&]<bool RESCALE>(std::bool_constant<RESCALE>) {
-                cfg_dpm_step_kernel<T, MASKED, RESCALE><<<grid, block, 0, stream>>>(
-                    (const T*)nu, (const T*)nc, (const T*)x, (const float*)x0_prev, (T*)out,
-                    (float*)x0_out, g, ca, cb, cc, cx, ce, total, MASKED ? *blend : MaskBlend{},
-                    factor);
+                dispatch_bool(noisy, [&]<bool NOISE>(std::bool_constant<NOISE>) {
+                    cfg_dpm_step_kernel<T, MASKED, RESCALE, NOISE><<<grid, block, 0, stream>>>(
+                        (const T*)nu, (const T*)nc, (const T*)x, (const float*)x0_prev, (T*)out,
+                        (float*)x0_out, g, ca, cb, cc, cx, ce, total,
+                        MASKED ? *blend : MaskBlend{}, factor, cn, key);
+                });
             });
         });
     });
+}
+
+namespace {
+
+// One thread per Philox block of the absolute stream: block q covers elements
+// 4q .. 4q + 3, of which those in [offset, offset + numel) are stored.
+__global__ void philox_normal_kernel(float* __restrict__ out, int64_t numel, int64_t offset,
+                                     int64_t nblocks, PhiloxKey key) {
+    const int64_t first = offset >> 2;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < nblocks; b += stride) {
+        float z[4];
+        philox_normal4(key, (uint64_t)(first + b), z);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t e = ((first + b) << 2) + j - offset;
+            if (e >= 0 && e < numel) out[e] = z[j];
+        }
+    }
+}
+
+}  // namespace
+
+void launch_philox_normal(float* out, int64_t numel, int64_t offset, uint64_t seed,
+                          uint32_t draw, hipStream_t stream) {
+    if (numel <= 0) return;
+    const int block = 256;
+    const int64_t nblocks = ((offset + numel - 1) >> 2) - (offset >> 2) + 1;
+    const StepNoise noise{1.f, seed, draw};
+    philox_normal_kernel<<<grid_for(nblocks, block), block, 0, stream>>>(out, numel, offset,
+                                                                         nblocks, philox_key(&noise));
 }
 
 namespace {

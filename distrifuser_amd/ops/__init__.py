@@ -11,6 +11,8 @@ from .conv import NativeConv2d, conv3x3_halo, pack_conv3x3_weight
 from .dispatch import (
     add_layer_norm,
     attention_kv_splits,
+    cfg_affine_step,
+    cfg_dpm_step,
     flash_attention,
     flash_attention_chunked,
     geglu,
@@ -25,6 +27,7 @@ from .dispatch import (
     masked_affine_step,
     masked_dpm_step,
     merge_attention,
+    philox_normal,
     tokens_add_nchw,
     use_hip,
     vae_attention,
@@ -36,6 +39,8 @@ __all__ = [
     "PlainGroupNorm",
     "add_layer_norm",
     "attention_kv_splits",
+    "cfg_affine_step",
+    "cfg_dpm_step",
     "layer_norm",
     "conv3x3_halo",
     "flash_attention",
@@ -52,6 +57,7 @@ __all__ = [
     "masked_dpm_step",
     "merge_attention",
     "pack_conv3x3_weight",
+    "philox_normal",
     "tokens_add_nchw",
     "use_hip",
     "vae_attention",

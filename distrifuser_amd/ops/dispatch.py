@@ -308,35 +308,84 @@ def _with_factor(factor) -> tuple:
     return () if factor is None else (factor,)
 
 
-def masked_affine_step(noise, x, init, init_noise, mask, g, ca, cb, sa, sb, factor=None):
+def _with_noise(step_noise) -> dict:
+    """The keyword of a noisy native step: none without noise, as _with_factor."""
+    return {} if step_noise is None else {"step_noise": step_noise}
+
+
+def philox_normal(numel: int, seed: int, draw: int, offset: int = 0, device=None) -> torch.Tensor:
+    """fp32 [numel]: the Philox4x32-10 / Box-Muller standard normals of
+    elements offset .. offset + numel - 1 of the stream (seed, draw), the noise
+    the stochastic scheduler steps add. A pure function of (seed, draw,
+    element index): see ``eager.philox_normal`` for the rule. One launch on a
+    GPU device; the eager twin elsewhere."""
+    dev = torch.device("cpu" if device is None else device)
+    if dev.type == "cuda" and not _force_eager():
+        index = torch.cuda.current_device() if dev.index is None else dev.index
+        return hip_ext().philox_normal(numel, seed, draw, offset, index)
+    return eager.philox_normal(numel, seed, draw, offset, dev)
+
+
+def cfg_affine_step(noise, x, g, ca, cb, factor=None, step_noise=None):
+    """CFG combine + affine scheduler update in one launch on GPU:
+
+        eps = nu + g*(nc - nu),   x' = ca*x + cb*eps (+ cn*z)
+
+    noise is the [2,C,h,w] pair. step_noise = (cn, seed, draw) adds the noise
+    term of a stochastic sampler, z = ``philox_normal(x.numel(), seed, draw)``
+    drawn inside the kernel; x must then be [1,C,h,w], and noise may also be
+    one branch's output in x's shape (eps = noise, g not read). cn == 0 gives
+    the bits of the call without step_noise."""
+    if use_hip(x) and x.dtype in _BOUNDARY_DTYPES:
+        return hip_ext().cfg_affine_step(noise, x, g, ca, cb, *_with_factor(factor),
+                                         **_with_noise(step_noise))
+    return eager.cfg_affine_step(noise, x, g, ca, cb, factor, step_noise)
+
+
+def cfg_dpm_step(noise, x, x0_prev, g, ca, cb, cc, cx, ce, factor=None, step_noise=None):
+    """CFG combine + DPM-Solver++(2M) update in one launch on GPU ->
+    (prev, x0 fp32): prev = ca*x + cb*eps + cc*x0_prev (+ cn*z), x0 = cx*x +
+    ce*eps. step_noise as in cfg_affine_step; x0 never sees it."""
+    if use_hip(x) and x.dtype in _BOUNDARY_DTYPES:
+        prev, x0 = hip_ext().cfg_dpm_step(noise, x, x0_prev, g, ca, cb, cc, cx, ce,
+                                          *_with_factor(factor), **_with_noise(step_noise))
+        return prev, x0
+    return eager.cfg_dpm_step(noise, x, x0_prev, g, ca, cb, cc, cx, ce, factor, step_noise)
+
+
+def masked_affine_step(noise, x, init, init_noise, mask, g, ca, cb, sa, sb, factor=None,
+                       step_noise=None):
     """Inpaint step of DDIM / Euler in one launch on GPU:
 
         eps = nu + g*(nc - nu)   (noise [2,C,h,w]; eps = noise for [1,C,h,w])
-        x'  = ca*x + cb*eps
+        x'  = ca*x + cb*eps (+ cn*z)
         out = m*x' + (1 - m)*(sa*init + sb*init_noise)
 
     x [1,C,h,w] in bf16, fp16 or fp32; init, init_noise fp32 [1,C,h,w]; mask
     fp32 with h*w elements, shared by the channels. factor (from
-    ``guidance_rescale_factor``, CFG pair only) scales eps first."""
+    ``guidance_rescale_factor``, CFG pair only) scales eps first. step_noise
+    as in cfg_affine_step."""
     if use_hip(x) and x.dtype in _BOUNDARY_DTYPES:
         return hip_ext().masked_affine_step(noise, x, _f32(init, x), _f32(init_noise, x),
                                             _f32(mask, x), g, ca, cb, sa, sb,
-                                            *_with_factor(factor))
-    return eager.masked_affine_step(noise, x, init, init_noise, mask, g, ca, cb, sa, sb, factor)
+                                            *_with_factor(factor), **_with_noise(step_noise))
+    return eager.masked_affine_step(noise, x, init, init_noise, mask, g, ca, cb, sa, sb, factor,
+                                    step_noise)
 
 
 def masked_dpm_step(noise, x, x0_prev, init, init_noise, mask, g, ca, cb, cc, cx, ce, sa, sb,
-                    factor=None):
+                    factor=None, step_noise=None):
     """Inpaint step of DPM-Solver++(2M): cfg_dpm_step with the blend of
     masked_affine_step on prev. Returns (prev, x0); x0 (fp32) is not blended.
-    factor as in masked_affine_step."""
+    factor and step_noise as in masked_affine_step."""
     if use_hip(x) and x.dtype in _BOUNDARY_DTYPES:
         prev, x0 = hip_ext().masked_dpm_step(noise, x, x0_prev, _f32(init, x),
                                              _f32(init_noise, x), _f32(mask, x), g, ca, cb, cc,
-                                             cx, ce, sa, sb, *_with_factor(factor))
+                                             cx, ce, sa, sb, *_with_factor(factor),
+                                             **_with_noise(step_noise))
         return prev, x0
     return eager.masked_dpm_step(noise, x, x0_prev, init, init_noise, mask, g, ca, cb, cc, cx,
-                                 ce, sa, sb, factor)
+                                 ce, sa, sb, factor, step_noise)
 
 
 def inpaint_unet_input(latents, mask, masked_latents, scale=1.0, copies=1):

@@ -211,41 +211,126 @@ def _mask_blend(xp, x, init, init_noise, mask, sa, sb):
     return (m * xp + (1.0 - m) * known).to(x.dtype)
 
 
-def cfg_affine_step(noise, x, g, ca, cb, factor=None):
-    """x' = ca*x + cb*eps of a CFG pair, eps scaled by factor when given."""
-    return (ca * x.float() + cb * _cfg_eps(noise, x, g, factor)).to(x.dtype)
+_PHILOX_M0, _PHILOX_M1 = 0xD2511F53, 0xCD9E8D57  # Random123 multipliers
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85  # Weyl key increments
+_MASK32 = 0xFFFFFFFF
 
 
-def cfg_dpm_step(noise, x, x0_prev, g, ca, cb, cc, cx, ce, factor=None):
+def _mulhilo32(m: int, c: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """(hi, lo) words of the 64-bit product m * c; c holds 32-bit values in
+    int64. The product is formed from c's 16-bit halves, so nothing passes 2^63."""
+    p0 = m * (c & 0xFFFF)
+    p1 = m * (c >> 16)
+    t = ((p1 & 0xFFFF) << 16) + p0
+    return (p1 >> 16) + (t >> 32), t & _MASK32
+
+
+def philox4x32(c0, c1, c2, c3, k0: int, k1: int):
+    """Philox4x32-10 (Random123 constants) in torch integer ops: counter words
+    c0..c3 (int64 tensors of 32-bit values, or ints) and key words k0, k1
+    (ints) -> the four output words, int64 tensors."""
+    c0, c1, c2, c3 = torch.broadcast_tensors(
+        *(torch.as_tensor(c, dtype=torch.int64) for c in (c0, c1, c2, c3)))
+    k0, k1 = int(k0) & _MASK32, int(k1) & _MASK32
+    for _ in range(10):
+        hi0, lo0 = _mulhilo32(_PHILOX_M0, c0)
+        hi1, lo1 = _mulhilo32(_PHILOX_M1, c2)
+        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+        k0, k1 = (k0 + _PHILOX_W0) & _MASK32, (k1 + _PHILOX_W1) & _MASK32
+    return c0, c1, c2, c3
+
+
+def philox_normal(numel: int, seed: int, draw: int, offset: int = 0, device=None) -> torch.Tensor:
+    """fp32 [numel]: the standard normals of elements offset .. offset + numel
+    - 1 of the stream (seed, draw): the rule of csrc/philox.h. Element i reads
+    Philox block q = i >> 2, counter (lo32(q), hi32(q), draw, 0), key
+    (lo32(seed), hi32(seed)); the words (r0, r1) and (r2, r3) give two
+    Box-Muller pairs in fp32,
+
+        u1 = ((ra >> 8) + 1) * 2^-24,  u2 = (rb >> 8) * 2^-24,
+        rad = sqrt(-2 ln u1),  (z_even, z_odd) = rad * (cos, sin)(2 pi u2),
+
+    and element i takes z[i & 3]. Integer ops and elementwise fp32 functions
+    only: it runs on any device, and it is the reference of the native op."""
+    if numel < 0 or offset < 0:
+        raise ValueError("philox_normal: numel and offset must be >= 0")
+    seed, draw = int(seed), int(draw)
+    if not 0 <= seed < 2 ** 64 or not 0 <= draw < 2 ** 32:
+        raise ValueError("philox_normal: seed must fit 64 bits and draw 32 bits, unsigned")
+    first = offset >> 2
+    nblocks = ((offset + numel - 1) >> 2) - first + 1 if numel else 0
+    q = torch.arange(first, first + nblocks, dtype=torch.int64, device=device)
+    r = philox4x32(q & _MASK32, q >> 32, torch.full_like(q, draw), torch.zeros_like(q),
+                   seed & _MASK32, seed >> 32)
+    two_pi = torch.tensor(6.283185307179586, dtype=torch.float32, device=q.device)
+    z = []
+    for ra, rb in ((r[0], r[1]), (r[2], r[3])):
+        u1 = ((ra >> 8) + 1).float() * 2.0 ** -24
+        u2 = (rb >> 8).float() * 2.0 ** -24
+        rad = torch.sqrt(-2.0 * torch.log(u1))
+        ang = two_pi * u2
+        z += [rad * torch.cos(ang), rad * torch.sin(ang)]
+    lead = offset - (first << 2)
+    return torch.stack(z, dim=1).reshape(-1)[lead:lead + numel]
+
+
+def _add_step_noise(xp: torch.Tensor, x: torch.Tensor, noise) -> torch.Tensor:
+    """x' + cn * z for noise = (cn, seed, draw), z indexed by the element's
+    offset in the one sample x [1,C,h,w]; x' itself for None or cn == 0."""
+    if noise is None:
+        return xp
+    cn, seed, draw = noise
+    if x.dim() != 4 or x.shape[0] != 1:
+        raise ValueError("a noisy step needs x [1,C,h,w] (one sample)")
+    if cn == 0:
+        return xp
+    z = philox_normal(x.numel(), seed, draw, device=x.device).reshape(x.shape)
+    return xp + cn * z
+
+
+def cfg_affine_step(noise, x, g, ca, cb, factor=None, step_noise=None):
+    """x' = ca*x + cb*eps of a CFG pair, eps scaled by factor when given.
+    step_noise = (cn, seed, draw) adds cn * z (``philox_normal``); noise may
+    then also be one branch's output in x's shape (eps = noise)."""
+    xp = ca * x.float() + cb * _cfg_eps(noise, x, g, factor)
+    return _add_step_noise(xp, x, step_noise).to(x.dtype)
+
+
+def cfg_dpm_step(noise, x, x0_prev, g, ca, cb, cc, cx, ce, factor=None, step_noise=None):
     """DPM-Solver++(2M) step of a CFG pair -> (prev, x0 fp32); eps scaled by
-    factor when given."""
+    factor when given. step_noise as in cfg_affine_step: added to prev alone."""
     eps = _cfg_eps(noise, x, g, factor)
     xf = x.float()
     prev = ca * xf + cb * eps
     if x0_prev is not None:
         prev = prev + cc * x0_prev.float()
-    return prev.to(x.dtype), cx * xf + ce * eps
+    return _add_step_noise(prev, x, step_noise).to(x.dtype), cx * xf + ce * eps
 
 
-def masked_affine_step(noise, x, init, init_noise, mask, g, ca, cb, sa, sb, factor=None):
+def masked_affine_step(noise, x, init, init_noise, mask, g, ca, cb, sa, sb, factor=None,
+                       step_noise=None):
     """Inpaint step of the affine schedulers (DDIM, Euler): x' = ca*x + cb*eps
     blended with the known region. noise [2,C,h,w] (CFG pair) or [1,C,h,w];
     x [1,C,h,w]; init, init_noise fp32 [1,C,h,w]; mask h*w elements, shared by
-    the channels. factor: the guidance_rescale factor, CFG pair only."""
+    the channels. factor: the guidance_rescale factor, CFG pair only.
+    step_noise = (cn, seed, draw) adds cn * z to x' before the blend."""
     xp = ca * x.float() + cb * _cfg_eps(noise, x, g, factor)
+    xp = _add_step_noise(xp, x, step_noise)
     return _mask_blend(xp, x, init, init_noise, mask, sa, sb)
 
 
 def masked_dpm_step(noise, x, x0_prev, init, init_noise, mask, g, ca, cb, cc, cx, ce, sa, sb,
-                    factor=None):
+                    factor=None, step_noise=None):
     """Inpaint step of DPM-Solver++(2M): prev = ca*x + cb*eps (+ cc*x0_prev)
     blended with the known region; x0 = cx*x + ce*eps (fp32) is the unmasked
-    step's. Returns (prev, x0). factor: the guidance_rescale factor."""
+    step's. Returns (prev, x0). factor: the guidance_rescale factor.
+    step_noise as in masked_affine_step."""
     eps = _cfg_eps(noise, x, g, factor)
     xf = x.float()
     prev = ca * xf + cb * eps
     if x0_prev is not None:
         prev = prev + cc * x0_prev.float()
+    prev = _add_step_noise(prev, x, step_noise)
     return _mask_blend(prev, x, init, init_noise, mask, sa, sb), cx * xf + ce * eps
 
 

@@ -27,7 +27,7 @@ from .models.unet import (SD15_INPAINT_UNET, SD15_UNET, SDXL_INPAINT_UNET, SDXL_
 from .models.vae import SD_VAE, SDXL_VAE, TINY_VAE, VAEDecoder, VAEEncoder
 from . import ops
 from .models import weights as weight_io
-from .schedulers import get_scheduler
+from .schedulers import scheduler_class
 from .schedulers.common import img2img_start
 from .utils.comm import PatchParallelismCommManager
 from .utils.config import DistriConfig
@@ -65,6 +65,8 @@ def _resolve_tokenizer(pretrained, vocab_size: int, subfolder: str = "tokenizer"
 _SCHEDULER_FILE_KEYS = ("prediction_type", "timestep_spacing", "rescale_betas_zero_snr",
                         "beta_start", "beta_end", "steps_offset", "num_train_timesteps")
 _SCHEDULER_KWARGS = _SCHEDULER_FILE_KEYS[:3]
+# what one scheduler class alone takes (its extra_config_keys)
+_SCHEDULER_CLASS_KWARGS = ("eta", "algorithm_type")
 
 
 def _load_scheduler(name: str, pretrained, kwargs: dict):
@@ -73,18 +75,27 @@ def _load_scheduler(name: str, pretrained, kwargs: dict):
     from ``prediction_type=`` / ``timestep_spacing=`` /
     ``rescale_betas_zero_snr=`` in ``kwargs`` (popped), which win over the
     file. A v-prediction checkpoint run as epsilon-prediction gives noise, so
-    the file is read whenever it is there."""
+    the file is read whenever it is there.
+
+    ``eta`` (ddim) and ``algorithm_type`` (dpm-solver) belong to one class
+    each: the file's value is taken only by that class, so a file saved with
+    one sampler loads into another, and as a keyword (popped) it raises
+    ``ValueError`` for a scheduler that lacks it."""
+    cls = scheduler_class(name)
+    file_keys = _SCHEDULER_FILE_KEYS + cls.extra_config_keys
     config = {}
     if pretrained is not None:
         path = os.path.join(pretrained, "scheduler", "scheduler_config.json")
         if os.path.isfile(path):
             with open(path, encoding="utf-8") as f:
                 on_file = json.load(f)
-            config = {k: on_file[k] for k in _SCHEDULER_FILE_KEYS if k in on_file}
-    for key in _SCHEDULER_KWARGS:
+            config = {k: on_file[k] for k in file_keys if k in on_file}
+    for key in _SCHEDULER_KWARGS + _SCHEDULER_CLASS_KWARGS:
         if key in kwargs:
+            if key in _SCHEDULER_CLASS_KWARGS and key not in cls.extra_config_keys:
+                raise ValueError(f"scheduler {name!r} ({cls.__name__}) takes no {key!r}")
             config[key] = kwargs.pop(key)
-    return get_scheduler(name, **config)
+    return cls(**config)
 
 
 def _check_guidance_rescale(guidance_rescale: float) -> float:
@@ -449,6 +460,11 @@ class _DistriPipelineBase:
         if self.unet.config.in_channels == 9 and mask is None:
             raise ValueError("a 9-channel inpaint U-Net needs image= and mask=")
         t_start, inpaint = 0, None
+        stochastic = getattr(self.scheduler, "stochastic", False)
+        if stochastic and generator is None:
+            # the fixed-seed generator the latents fall back to, kept to draw
+            # the noise seed after them (the same on every rank)
+            generator = torch.Generator().manual_seed(0)
         if image is None:
             latents = self._prepare_latents(1, generator)
         elif mask is None:
@@ -458,6 +474,13 @@ class _DistriPipelineBase:
             latents, t_start, inpaint = self._inpaint_latents(
                 image, mask, 1.0 if strength is None else strength, num_inference_steps,
                 generator)
+        if stochastic:
+            # one draw seeds every step's noise (a counter-based generator in
+            # the fused step kernels): every rank, holding an equal generator,
+            # adds the same noise. A deterministic scheduler draws nothing.
+            device = generator.device if hasattr(generator, "device") else torch.device("cpu")
+            seed = torch.randint(0, 2**63 - 1, (1,), generator=generator, device=device)
+            self.scheduler.set_noise_seed(int(seed))
         latents = self._denoise(latents, embeds, added_cond_kwargs, num_inference_steps,
                                 guidance_scale, t_start, inpaint, guidance_rescale)
         return self._decode(latents, output_type)

@@ -23,6 +23,14 @@ Algorithm 1).
 is an argument of ``guided_step`` / ``masked_step``: the CFG result is scaled
 by phi * std(cond) / std(cfg) + (1 - phi) before the step, on the raw model
 output whatever the prediction type.
+
+The stochastic samplers (Euler ancestral, DDIM with eta > 0, DPM-Solver++ SDE)
+add one term ``cn * z`` to the same affine step, z ~ N(0, 1). z is never a
+``torch.randn`` draw: it is ``ops.philox_normal(numel, seed, draw)``, a pure
+function of the seed given to ``set_noise_seed``, of the number of steps taken
+since ``set_timesteps`` / ``set_begin_index`` and of the element index, which
+the fused step kernels evaluate in place. Equal seeds give equal noise on every
+rank, in every dtype and on the CPU.
 """
 
 from __future__ import annotations
@@ -47,6 +55,11 @@ def rescale_zero_terminal_snr(betas: torch.Tensor) -> torch.Tensor:
 
 class SchedulerBase:
     order = 1
+    # constructor arguments (and config() keys) of one class alone: a
+    # scheduler_config.json written by another class may hold them
+    extra_config_keys: tuple[str, ...] = ()
+    _noise_seed = 0
+    _draw = 0  # steps taken since set_timesteps / set_begin_index
 
     def __init__(
         self,
@@ -125,6 +138,34 @@ class SchedulerBase:
     def scale_model_input(self, sample: torch.Tensor, timestep=None) -> torch.Tensor:
         return sample
 
+    # -- the noise term of the stochastic samplers ---------------------------------
+
+    @property
+    def stochastic(self) -> bool:
+        """Whether steps add noise (and ``set_noise_seed`` matters)."""
+        return False
+
+    def set_noise_seed(self, seed: int) -> None:
+        """The 64-bit seed of the steps' noise (default 0). It outlives
+        ``set_timesteps``; the draw counter does not."""
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError(f"noise seed must be in [0, 2**64), got {seed}")
+        self._noise_seed = seed
+
+    def _take_draw(self, cn: float):
+        """(cn, seed, draw) of the step about to run, None for a deterministic
+        scheduler; either way the draw counter moves on, once per step."""
+        draw = self._draw
+        self._draw += 1
+        return (float(cn), self._noise_seed, draw) if self.stochastic else None
+
+    def _add_noise_eager(self, prev: torch.Tensor, cn: float) -> torch.Tensor:
+        """prev (fp32) + cn * z, the eager composition of a step's noise term."""
+        from ..ops.eager import _add_step_noise
+
+        return _add_step_noise(prev, prev, self._take_draw(cn))
+
     # -- guidance_rescale ---------------------------------------------------------
 
     @staticmethod
@@ -193,12 +234,15 @@ class SchedulerBase:
         with known = ``add_noise(init, init_noise, t_next)``, or init itself
         after the last step. mask (1 = repaint) has one value per latent
         pixel; init and init_noise are fp32 [1,C,h,w]. The scheduler state
-        advances as in an unmasked step. One fused kernel on GPU; elsewhere
+        advances as in an unmasked step, and a stochastic scheduler's noise
+        term is part of x', added before the blend. One fused kernel on GPU; elsewhere
         the composition of ``step`` and ``add_noise`` in fp32.
         ``guidance_rescale`` > 0 rescales the CFG result first (the factor op,
         then the fused step with it); without a CFG pair it is not read."""
         from ..ops import use_hip
 
+        if self.stochastic and (sample.dim() != 4 or sample.shape[0] != 1):
+            raise ValueError("a stochastic scheduler steps one sample [1,C,h,w]")
         factor = self._rescale_factor(noise, sample, guidance_scale, guidance_rescale)
         if use_hip(sample):
             if factor is None:
@@ -231,6 +275,7 @@ class SchedulerBase:
         if not 0 <= t_start < n:
             raise ValueError(f"t_start must be in [0, {n}), got {t_start}")
         self.timesteps = self.timesteps[t_start:]
+        self._draw = 0
 
 
 def img2img_start(num_inference_steps: int, strength: float) -> int:

@@ -1,4 +1,13 @@
-"""DPM-Solver++ (2M, multistep; epsilon- or v-prediction)."""
+"""DPM-Solver++ (2M, multistep; epsilon- or v-prediction), and its SDE variant
+(``algorithm_type="sde-dpmsolver++"``, the "DPM++ 2M SDE" sampler): with
+A = (s_p / s_t) e^-h and B = a_p (1 - e^-2h),
+
+    first order: prev = A x + B x0 + cn z
+    2M:          prev = A x + B (1 + 0.5 / r0) x0 - (0.5 B / r0) x0_prev + cn z
+    cn = s_p sqrt(1 - e^-2h),   z ~ N(0, 1)
+
+which is the deterministic update's affine form with other coefficients, plus
+the noise term of the fused kernel."""
 
 from __future__ import annotations
 
@@ -8,8 +17,16 @@ from .common import SchedulerBase
 
 
 class DPMSolverMultistepScheduler(SchedulerBase):
-    def __init__(self, *args, solver_order: int = 2, **kwargs):
+    extra_config_keys = ("algorithm_type",)
+    ALGORITHM_TYPES = ("dpmsolver++", "sde-dpmsolver++")
+
+    def __init__(self, *args, solver_order: int = 2, algorithm_type: str = "dpmsolver++",
+                 **kwargs):
         super().__init__(*args, **kwargs)
+        if algorithm_type not in self.ALGORITHM_TYPES:
+            raise ValueError(
+                f"algorithm_type must be one of {self.ALGORITHM_TYPES}, got {algorithm_type!r}")
+        self.algorithm_type = algorithm_type
         self.solver_order = solver_order
         acp = self._finite_alphas_cumprod()
         self.alpha_t = acp.sqrt()
@@ -19,6 +36,13 @@ class DPMSolverMultistepScheduler(SchedulerBase):
         self._t_prev: int | None = None
         self._step_index = 0
 
+    @property
+    def stochastic(self) -> bool:
+        return self.algorithm_type == "sde-dpmsolver++"
+
+    def config(self) -> dict:
+        return {**super().config(), "algorithm_type": self.algorithm_type}
+
     def set_timesteps(self, num_inference_steps: int, device=None) -> None:
         self.num_inference_steps = num_inference_steps
         self.timesteps = self._spaced_timesteps(num_inference_steps)
@@ -27,6 +51,7 @@ class DPMSolverMultistepScheduler(SchedulerBase):
         self._x0_prev = None
         self._t_prev = None
         self._step_index = 0
+        self._draw = 0
 
     def set_begin_index(self, t_start: int) -> None:
         super().set_begin_index(t_start)
@@ -39,7 +64,30 @@ class DPMSolverMultistepScheduler(SchedulerBase):
         idx = int((self.timesteps == t).nonzero()[0])
         return int(self.timesteps[idx + 1]) if idx + 1 < len(self.timesteps) else 0
 
+    def _noise_coeff(self, timestep) -> float:
+        """cn = s_p * sqrt(1 - e^-2h) of the SDE step at ``timestep``, else 0.0."""
+        if not self.stochastic:
+            return 0.0
+        import math
+
+        t = int(timestep)
+        t_prev = self._prev_timestep(t)
+        h = float(self.lambda_t[t_prev]) - float(self.lambda_t[t])
+        return float(self.sigma_t[t_prev]) * math.sqrt(max(1.0 - math.exp(-2.0 * h), 0.0))
+
     def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor) -> torch.Tensor:
+        from ..ops import cfg_dpm_step, use_hip
+
+        if self.stochastic and use_hip(sample):
+            # no CFG pair: still the one fused launch, which draws the noise
+            first, coeffs = self._affine_coeffs(timestep)
+            prev, x0 = cfg_dpm_step(
+                model_output, sample, None if first else self._x0_prev, 1.0, *coeffs,
+                step_noise=self._take_draw(self._noise_coeff(timestep)))
+            self._x0_prev = x0
+            self._t_prev = int(timestep)
+            self._step_index += 1
+            return prev
         t = int(timestep)
         t_prev = self._prev_timestep(t)
         x = sample.float()
@@ -50,7 +98,16 @@ class DPMSolverMultistepScheduler(SchedulerBase):
         x0 = a_t * x - s_t * eps if self.v_prediction else (x - s_t * eps) / a_t
 
         h = l_p - l_t
-        if self._x0_prev is None or self.solver_order == 1 or self._step_index == len(self.timesteps) - 1:
+        first = (self._x0_prev is None or self.solver_order == 1
+                 or self._step_index == len(self.timesteps) - 1)
+        if self.stochastic:
+            lead = (s_p / s_t) * torch.exp(-h)
+            b = a_p * (1.0 - torch.exp(-2.0 * h))
+            prev = lead * x + b * x0
+            if not first:
+                r0 = (l_t - self.lambda_t[self._t_prev]) / h
+                prev = prev + 0.5 * b * ((x0 - self._x0_prev) / r0)
+        elif first:
             # first-order (DPM-Solver++ 1S) update
             prev = (s_p / s_t) * x - a_p * (torch.exp(-h) - 1.0) * x0
         else:
@@ -65,10 +122,11 @@ class DPMSolverMultistepScheduler(SchedulerBase):
                 - 0.5 * a_p * (torch.exp(-h) - 1.0) * d1
             )
 
+        cn = self._noise_coeff(timestep)
         self._x0_prev = x0
         self._t_prev = t
         self._step_index += 1
-        return prev.to(sample.dtype)
+        return self._add_noise_eager(prev, cn).to(sample.dtype)
 
     def guided_step(self, noise: torch.Tensor, timestep, sample: torch.Tensor,
                     guidance_scale: float, guidance_rescale: float = 0.0) -> torch.Tensor:
@@ -81,8 +139,11 @@ class DPMSolverMultistepScheduler(SchedulerBase):
         v-prediction changes x0 alone, cx = a_t and ce = -s_t, and with it
             ca = s_p/s_t - C'*cx,  cb = -C'*ce.
         guidance_rescale > 0 adds the two launches of the factor op in front.
+        The SDE variant: exp(-2h) for exp(-h) in C, s_p/s_t * exp(-h) for
+        s_p/s_t, and the kernel's noise term.
         """
         from ..ops import hip_ext, use_hip
+        from ..ops.dispatch import _with_noise
 
         factor = self._rescale_factor(noise, sample, guidance_scale, guidance_rescale)
         if not use_hip(noise):
@@ -95,7 +156,8 @@ class DPMSolverMultistepScheduler(SchedulerBase):
         first, coeffs = self._affine_coeffs(timestep)
         prev, x0 = hip_ext().cfg_dpm_step(
             noise, sample, None if first else self._x0_prev, guidance_scale, *coeffs,
-            *(() if factor is None else (factor,)))
+            *(() if factor is None else (factor,)),
+            **_with_noise(self._take_draw(self._noise_coeff(timestep))))
         self._x0_prev = x0
         self._t_prev = int(timestep)
         self._step_index += 1
@@ -114,6 +176,10 @@ class DPMSolverMultistepScheduler(SchedulerBase):
 
         h = l_p - l_t
         C = a_p * (math.exp(-h) - 1.0)
+        lead = s_p / s_t
+        if self.stochastic:
+            C = a_p * (math.exp(-2.0 * h) - 1.0)  # -B
+            lead = lead * math.exp(-h)  # A
         first = (self._x0_prev is None or self.solver_order == 1
                  or self._step_index == len(self.timesteps) - 1)
         if first:
@@ -125,8 +191,8 @@ class DPMSolverMultistepScheduler(SchedulerBase):
             cc = 0.5 * C / r0
         if self.v_prediction:
             cx, ce = a_t, -s_t
-            return first, (s_p / s_t - cprime * cx, -cprime * ce, cc, cx, ce)
-        ca = s_p / s_t - cprime / a_t
+            return first, (lead - cprime * cx, -cprime * ce, cc, cx, ce)
+        ca = lead - cprime / a_t
         cb = cprime * s_t / a_t
         cx = 1.0 / a_t
         ce = -s_t / a_t
@@ -139,7 +205,8 @@ class DPMSolverMultistepScheduler(SchedulerBase):
         first, coeffs = self._affine_coeffs(timestep)
         sa, sb = self._known_coeffs(timestep)
         prev, x0 = masked_dpm_step(noise, sample, None if first else self._x0_prev, init,
-                                   init_noise, mask, guidance_scale, *coeffs, sa, sb, factor)
+                                   init_noise, mask, guidance_scale, *coeffs, sa, sb, factor,
+                                   self._take_draw(self._noise_coeff(timestep)))
         self._x0_prev = x0
         self._t_prev = int(timestep)
         self._step_index += 1

@@ -26,6 +26,7 @@ class EulerDiscreteScheduler(SchedulerBase):
             self.timesteps = self.timesteps.to(device)
         self.init_noise_sigma = float((self.sigmas.max() ** 2 + 1) ** 0.5)
         self._step_index = 0
+        self._draw = 0
 
     def set_begin_index(self, t_start: int) -> None:
         super().set_begin_index(t_start)
@@ -43,9 +44,23 @@ class EulerDiscreteScheduler(SchedulerBase):
         sigma = self.sigmas[self._step_index]
         return sample / float((sigma**2 + 1) ** 0.5)
 
+    def _target_sigma(self) -> tuple[torch.Tensor, float]:
+        """The sigma the Euler step lands on, and the coefficient of the noise
+        it then adds: (sigma_next, 0.0) here."""
+        return self.sigmas[self._step_index + 1], 0.0
+
     def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor) -> torch.Tensor:
+        from ..ops import cfg_affine_step, use_hip
+
+        sigma_next, cn = self._target_sigma()
+        if self.stochastic and use_hip(sample):
+            # no CFG pair: still the one fused launch, which draws the noise
+            ca, cb = self._affine_coeffs()
+            self._step_index += 1
+            return cfg_affine_step(model_output, sample, 1.0, ca, cb,
+                                   step_noise=self._take_draw(cn))
         sigma = self.sigmas[self._step_index].to(sample.device)
-        sigma_next = self.sigmas[self._step_index + 1].to(sample.device)
+        sigma_next = sigma_next.to(sample.device)
         x = sample.float()
         eps = model_output.float()
         if self.v_prediction:
@@ -55,7 +70,7 @@ class EulerDiscreteScheduler(SchedulerBase):
         # epsilon prediction: derivative d = eps; x_{t+1} = x + d * (s_next - s)
         prev = x + eps * (sigma_next - sigma)
         self._step_index += 1
-        return prev.to(sample.dtype)
+        return self._add_noise_eager(prev, cn).to(sample.dtype)
 
     def guided_step(self, noise: torch.Tensor, timestep, sample: torch.Tensor,
                     guidance_scale: float, guidance_rescale: float = 0.0) -> torch.Tensor:
@@ -63,14 +78,16 @@ class EulerDiscreteScheduler(SchedulerBase):
         # affine in (x, eps): ca = 1, cb = sigma_next - sigma); guidance_rescale
         # > 0 adds the two launches of the factor op in front of it
         from ..ops import hip_ext, use_hip
+        from ..ops.dispatch import _with_noise
 
         factor = self._rescale_factor(noise, sample, guidance_scale, guidance_rescale)
         if use_hip(noise):
             ca, cb = self._affine_coeffs()
+            nkw = _with_noise(self._take_draw(self._target_sigma()[1]))
             self._step_index += 1
             if factor is None:
-                return hip_ext().cfg_affine_step(noise, sample, guidance_scale, ca, cb)
-            return hip_ext().cfg_affine_step(noise, sample, guidance_scale, ca, cb, factor)
+                return hip_ext().cfg_affine_step(noise, sample, guidance_scale, ca, cb, **nkw)
+            return hip_ext().cfg_affine_step(noise, sample, guidance_scale, ca, cb, factor, **nkw)
         if factor is not None:
             return self._guided_step_eager(noise, timestep, sample, guidance_scale, factor)
         nu, nc = noise.float().chunk(2)
@@ -102,6 +119,7 @@ class EulerDiscreteScheduler(SchedulerBase):
 
         sa, sb = self._known_coeffs(timestep)
         ca, cb = self._affine_coeffs()
+        step_noise = self._take_draw(self._target_sigma()[1])
         self._step_index += 1
         return masked_affine_step(noise, sample, init, init_noise, mask, guidance_scale, ca, cb,
-                                  sa, sb, factor)
+                                  sa, sb, factor, step_noise)

@@ -32,7 +32,13 @@ def get_args():
                    help="height [width]")
     p.add_argument("--guidance_scale", type=float, default=5.0)
     p.add_argument("--scheduler", type=str, default="ddim",
-                   choices=["ddim", "euler", "dpm-solver"])
+                   choices=["ddim", "euler", "euler-a", "dpm-solver"],
+                   help="euler-a (Euler ancestral) adds fresh noise every step")
+    p.add_argument("--eta", type=float, default=None,
+                   help="ddim only: eta in [0, 1]; > 0 adds the DDIM noise term")
+    p.add_argument("--algorithm_type", type=str, default=None,
+                   choices=["dpmsolver++", "sde-dpmsolver++"],
+                   help="dpm-solver only: sde-dpmsolver++ is DPM++ 2M SDE")
     p.add_argument("--prediction_type", type=str, default=None,
                    choices=["epsilon", "v_prediction"],
                    help="overrides the checkpoint's scheduler_config.json (epsilon without one)")
@@ -79,7 +85,8 @@ def main():
         use_cuda_graph=not args.no_cuda_graph and torch.cuda.is_available(),
     )
     dtype = torch.bfloat16 if torch.cuda.is_available() else torch.float32
-    sched_kw = {} if args.prediction_type is None else {"prediction_type": args.prediction_type}
+    sched_kw = {k: v for k, v in (("prediction_type", args.prediction_type), ("eta", args.eta),
+                                  ("algorithm_type", args.algorithm_type)) if v is not None}
     pipe = DistriSDXLPipeline.from_pretrained(
         cfg, torch_dtype=dtype, scheduler=args.scheduler,
         pretrained_model_name_or_path=args.pretrained, preset=args.preset, **sched_kw,

@@ -1,7 +1,9 @@
 """Minimal SD1.5 usage example (parity with the reference's sd_example.py).
 
 --prediction_type v_prediction --guidance_rescale 0.7 is the setting of the
-SD 2.x 768 checkpoints."""
+SD 2.x 768 checkpoints. --scheduler euler-a, --eta 1.0 (ddim) and
+--scheduler dpm-solver --algorithm_type sde-dpmsolver++ are the stochastic
+samplers: the steps' noise is seeded from the generator below."""
 
 import os
 import sys
@@ -18,13 +20,22 @@ from distrifuser_amd import DistriConfig, DistriSDPipeline
 parser = argparse.ArgumentParser()
 parser.add_argument("--prediction_type", default="epsilon", choices=["epsilon", "v_prediction"])
 parser.add_argument("--guidance_rescale", type=float, default=0.0)
+parser.add_argument("--scheduler", default="ddim",
+                    choices=["ddim", "euler", "euler-a", "dpm-solver"])
+parser.add_argument("--eta", type=float, default=None, help="ddim only, in [0, 1]")
+parser.add_argument("--algorithm_type", default=None,
+                    choices=["dpmsolver++", "sde-dpmsolver++"], help="dpm-solver only")
 args = parser.parse_args()
+sched_kw = {k: v for k, v in (("eta", args.eta), ("algorithm_type", args.algorithm_type))
+            if v is not None}
 
 distri_config = DistriConfig(height=512, width=512, mode="stale_gn")
 pipeline = DistriSDPipeline.from_pretrained(
     distri_config,
     torch_dtype=torch.bfloat16 if torch.cuda.is_available() else torch.float32,
     prediction_type=args.prediction_type,
+    scheduler=args.scheduler,
+    **sched_kw,
 )
 
 pipeline.set_progress_bar_config(disable=distri_config.rank != 0)
