@@ -27,7 +27,7 @@ __global__ __launch_bounds__(WPB* WAVE_SIZE) void ln_kernel(
     const uint16_t* xp = x + row * C;
     const uint16_t* rp = res ? res + row * C : nullptr;
     float v[VPT][8];
-    float s = 0.f, ss = 0.f;
+    float s = 0.f;
 #pragma unroll
     for (int k = 0; k < VPT; ++k) {
         const int d0 = (k * WAVE_SIZE + lane) * 8;
@@ -41,7 +41,6 @@ __global__ __launch_bounds__(WPB* WAVE_SIZE) void ln_kernel(
                 if (rp) f += b16_to_f32<F16>((uint16_t)rv[j]);
                 v[k][j] = f;
                 s += f;
-                ss += f * f;
             }
             if (sum_out) {
                 uint16_t sv[8];
@@ -57,9 +56,25 @@ __global__ __launch_bounds__(WPB* WAVE_SIZE) void ln_kernel(
         }
     }
     s = wave_all_reduce_sum(s);
-    ss = wave_all_reduce_sum(ss);
     const float mean = s / (float)C;
-    const float var = fmaxf(ss / (float)C - mean * mean, 0.f);
+    // Two-pass variance over the row held in registers: sum (x - mean)^2 keeps
+    // its precision when |mean| >> std, where E[x^2] - mean^2 cancels. Lanes
+    // past C hold zeros, which were harmless in the sum and are not in
+    // (0 - mean)^2: they stay out.
+    float sq = 0.f;
+#pragma unroll
+    for (int k = 0; k < VPT; ++k) {
+        const int d0 = (k * WAVE_SIZE + lane) * 8;
+        if (d0 < C) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float d = v[k][j] - mean;
+                sq += d * d;
+            }
+        }
+    }
+    sq = wave_all_reduce_sum(sq);
+    const float var = fmaxf(sq / (float)C, 0.f);
     const float inv = __frsqrt_rn(var + eps);
 
     uint16_t* yp = y + row * C;

@@ -8,6 +8,15 @@ exact edge-shape suites of their own:
 * tests/test_vae_attention_edges_gpu.py: VAE attention as an exact row
   gather at L around the 32-token tile, and peaked/stepped scores that pin
   the tail mask, the split-K d-slices and the running-max rescale.
+The element-wise kernels have float64-bounded edge suites (bounds derived
+from the kernel source, never from its output):
+* tests/test_layernorm_edges_gpu.py: rows known to the bit at every VPT
+  dispatch boundary, the once-rounded add_layer_norm sum, a NaN arena, and a
+  mean/std conditioning ladder;
+* tests/test_groupnorm_apply_edges_gpu.py: GroupNorm apply with supplied
+  moments on both paths, every dtype, and a second grid-stride trip;
+* tests/test_geglu_edges_gpu.py: every finite 16-bit gate, NaN containment,
+  which half is which, and a second grid-stride trip.
 
 Run on an MI355X box: pytest tests -m gpu -x -q"""
 
