@@ -426,6 +426,31 @@ at::Tensor flash_attention(const at::Tensor& q, const at::Tensor& k, const at::T
     return flash_plain({flash_params(q, k, v)}, q);
 }
 
+// FP8 pre-pass alone: the quantised KV records of (k, v), uint8
+// [B*H, tiles, ATTN_FP8_TILE_BYTES]. q supplies B, H and the dtype.
+at::Tensor attn_quant_kv_p(const FlashAttnParams& p, const at::Tensor& q) {
+    TORCH_CHECK(p.Dh == 64, "fp8 attention: head_dim must be 64, got ", p.Dh);
+    auto ws = at::empty({(long)p.B * p.H, (long)attn_fp8_num_tiles(p.NC * p.LC),
+                         (long)ATTN_FP8_TILE_BYTES},
+                        q.options().dtype(at::kByte));
+    launch_attn_quant_kv(p, ws.data_ptr<uint8_t>(), dtype_of(q), cur_stream());
+    return ws;
+}
+at::Tensor attn_quant_kv(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v) {
+    return attn_quant_kv_p(flash_params(q, k, v), q);
+}
+
+// e4m3 attention, head_dim 64: the pre-pass, then the kernel, on the current
+// stream; the workspace comes from the caching allocator (safe under graph
+// capture). -> logical [B,H,Lq,64], a view of [B,Lq,H,64]
+at::Tensor flash_attention_fp8(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v) {
+    FlashAttnLseParams p{flash_params(q, k, v)};
+    auto ws = attn_quant_kv_p(p, q);
+    auto o = flash_out(p, q);
+    launch_flash_attention_fp8(p, ws.data_ptr<uint8_t>(), dtype_of(q), cur_stream());
+    return o.permute({0, 2, 1, 3});
+}
+
 // A split-KV request: the params, S = the number of splits actually used
 // (kv_splits clamped to the number of 128-token tiles) and the fp32 workspace
 // shapes that go with it, o_part [S,B,Lq,H,D] and lse_part [S,B,H,Lq]
@@ -746,6 +771,22 @@ std::vector<at::Tensor> mfma_probe32(const at::Tensor& a, const at::Tensor& b) {
                         cur_stream());
     return {d};
 }
+
+// a, b: int32 [64][8] (four e4m3 bytes each); sa, sb: int32 [64] (four E8M0 bytes)
+std::vector<at::Tensor> mfma_probe_fp8(const at::Tensor& a, const at::Tensor& b,
+                                       const at::Tensor& sa, const at::Tensor& sb,
+                                       int64_t opsel_a, int64_t opsel_b) {
+    for (const auto* t : {&a, &b, &sa, &sb})
+        TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt && t->is_contiguous(),
+                    "mfma_probe_fp8: contiguous int32 CUDA tensors");
+    TORCH_CHECK(a.numel() == 512 && b.numel() == 512 && sa.numel() == 64 && sb.numel() == 64);
+    TORCH_CHECK(opsel_a >= 0 && opsel_a < 4 && opsel_b >= 0 && opsel_b < 4);
+    auto d = at::zeros({64, 16}, a.options().dtype(at::kFloat));
+    launch_mfma_probe_fp8(a.data_ptr<int>(), b.data_ptr<int>(), sa.data_ptr<int>(),
+                          sb.data_ptr<int>(), (int)opsel_a, (int)opsel_b, d.data_ptr<float>(),
+                          cur_stream());
+    return {d};
+}
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -776,6 +817,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("numel"), pybind11::arg("seed"), pybind11::arg("draw"),
           pybind11::arg("offset") = 0, pybind11::arg("device_index") = 0);
     m.def("flash_attention", &flash_attention, "bf16/fp16 flash attention (chunked stale KV)");
+    m.def("flash_attention_fp8", &flash_attention_fp8,
+          "e4m3 flash attention, head_dim 64: KV quantisation pre-pass + kernel");
+    m.def("attn_quant_kv", &attn_quant_kv, "the e4m3 KV pre-pass alone -> uint8 tile records");
     m.def("flash_attention_ext", &flash_attention_ext,
           "flash attention with split-KV and optional log-sum-exp -> [out] or [out, lse]",
           pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"),
@@ -817,4 +861,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("pad_lo") = 1);
     m.def("mfma_probe", &mfma_probe, "dump mfma_f32_16x16x32_bf16 fragment mapping");
     m.def("mfma_probe32", &mfma_probe32, "dump mfma_f32_32x32x16_bf16 fragment mapping");
+    m.def("mfma_probe_fp8", &mfma_probe_fp8,
+          "dump mfma_scale_f32_32x32x64_f8f6f4 (e4m3, E8M0 scales) fragment mapping");
 }

@@ -217,9 +217,26 @@ int flash_attention_num_splits(int64_t lkv, int splits);
 void launch_flash_attention(const FlashAttnLseParams& p, int splits, int dtype,
                             hipStream_t stream);
 
+// ---- FP8 (e4m3) self-attention, head_dim 64 (attention_fp8.hip) ------------------
+// Two launches over the same FlashAttnParams (Dh == 64; p.o is read by the
+// second alone). launch_attn_quant_kv quantises K and V into ws: per (b, h)
+// attn_fp8_num_tiles(Lkv) records of ATTN_FP8_TILE_BYTES, one per 128 tokens,
+// every byte written (no initialisation needed). launch_flash_attention_fp8
+// quantises Q in registers and writes 16-bit O [B, Lq, H, 64].
+constexpr int ATTN_FP8_TILE_BYTES = 16768;
+int64_t attn_fp8_num_tiles(int64_t lkv);
+void launch_attn_quant_kv(const FlashAttnParams& p, uint8_t* ws, int dtype, hipStream_t stream);
+void launch_flash_attention_fp8(const FlashAttnParams& p, const uint8_t* ws, int dtype,
+                                hipStream_t stream);
+
 // ---- fragment-layout probes: one wave, a/b fp32 [64][8], d fp32 [64][4] / [64][16] ----
 void launch_mfma_probe(const float* a, const float* b, float* d, hipStream_t stream);
 void launch_mfma_probe32(const float* a, const float* b, float* d, hipStream_t stream);
+// one v_mfma_scale_f32_32x32x64_f8f6f4: a/b [64][8] dwords of four e4m3 bytes,
+// scale_a/scale_b [64] dwords of four E8M0 bytes of which op_sel (0..3) names
+// one, d fp32 [64][16]
+void launch_mfma_probe_fp8(const int* a, const int* b, const int* scale_a, const int* scale_b,
+                           int opsel_a, int opsel_b, float* d, hipStream_t stream);
 
 // ---- merge of attention partials ----------------------------------------------
 // out[b,q,h,:] = sum_s w_s o_parts[s,b,q,h,:] / sum_s w_s, w_s = exp(lse_s - max_s lse_s);

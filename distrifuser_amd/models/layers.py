@@ -45,10 +45,16 @@ class PlainSelfAttention(nn.Module):
         k, v = self.to_kv(x).split(inner, dim=-1)
         k = k.view(b, l, self.heads, self.dim_head).transpose(1, 2)
         v = v.view(b, l, self.heads, self.dim_head).transpose(1, 2)
-        splits = 1
+        splits, fp8 = 1, None
         if self.config is not None:
-            splits = self.config.attn_splits(b, self.heads, l, l, self.dim_head)
-        out = ops.flash_attention(q, k, v, kv_splits=splits).transpose(1, 2).reshape(b, l, inner)
+            fp8 = self.config.attn_compute_dtype(self.dim_head)
+            if fp8 is None:
+                splits = self.config.attn_splits(b, self.heads, l, l, self.dim_head)
+        if fp8 is None:
+            out = ops.flash_attention(q, k, v, kv_splits=splits)
+        else:
+            out = ops.flash_attention(q, k, v, compute_dtype=fp8)
+        out = out.transpose(1, 2).reshape(b, l, inner)
         return self.to_out(out)
 
 

@@ -78,6 +78,26 @@ def _check_kv_splits(kv_splits: int) -> int:
     return kv_splits
 
 
+def _check_compute_dtype(compute_dtype, kv_splits: int, return_lse: bool) -> bool:
+    """True for "fp8"; None is the 16-bit path."""
+    if compute_dtype is None:
+        return False
+    if compute_dtype != "fp8":
+        raise ValueError(f"compute_dtype must be None or 'fp8', got {compute_dtype!r}")
+    if kv_splits > 1 or return_lse:
+        raise ValueError("compute_dtype='fp8' has no split-KV or log-sum-exp mode")
+    return True
+
+
+def _flash_fp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+    """q [B,H,Lq,D], k/v [B,H,Lkv,D] or chunked [B,H,NC,LC,D] -> [B,H,Lq,D]."""
+    if use_hip(q) and _flash_ok(q, k, v) and q.shape[-1] == 64:
+        return hip_ext().flash_attention_fp8(q, k, v)
+    if k.dim() == 5:
+        k, v = k.flatten(2, 3), v.flatten(2, 3)
+    return eager.flash_attention_fp8(q, k, v)
+
+
 def flash_attention(
     q: torch.Tensor,
     k: torch.Tensor,
@@ -85,6 +105,7 @@ def flash_attention(
     *,
     kv_splits: int = 1,
     return_lse: bool = False,
+    compute_dtype: str | None = None,
 ):
     """Attention over (possibly strided) full-sequence KV.
 
@@ -94,8 +115,17 @@ def flash_attention(
     result up to fp32 rounding, a fuller grid when Lq is short. return_lse
     adds the fp32 softmax log-sum-exp [B, H, Lq]: returns (out, lse). The
     eager path accepts kv_splits and ignores it.
+
+    compute_dtype="fp8": q, k, v and the probabilities are e4m3 with
+    power-of-two block scales, accumulation stays fp32 (the rule is
+    ``eager.flash_attention_fp8``). bf16 / fp16 inputs with head_dim 64 run the
+    gfx950 fp8 kernels; CPU, DFA_FORCE_EAGER=1, fp32 and other head dims run
+    that eager twin, so "fp8" always means the same arithmetic. Not with
+    kv_splits > 1 or return_lse.
     """
     _check_kv_splits(kv_splits)
+    if _check_compute_dtype(compute_dtype, kv_splits, return_lse):
+        return _flash_fp8(q, k, v)
     if use_hip(q) and _flash_ok(q, k, v):
         if kv_splits == 1 and not return_lse:
             return hip_ext().flash_attention(q, k, v)
@@ -108,17 +138,24 @@ def flash_attention(
 
 
 def flash_attention_chunked(
-    q: torch.Tensor, kv_chunks: torch.Tensor, heads: int, dim_head: int, kv_splits: int = 1
+    q: torch.Tensor, kv_chunks: torch.Tensor, heads: int, dim_head: int, kv_splits: int = 1,
+    compute_dtype: str | None = None,
 ) -> torch.Tensor:
     """Displaced-patch attention: q [B, Lq, inner]; kv_chunks is the flat comm
     buffer viewed as [n_peers, B, L_local, 2*inner] (strided — peer rows live
     in the flat buffer). On GPU the gfx950 kernel walks the chunks in place
     (kv_splits as in flash_attention; a split may start mid-chunk); the eager
-    path materializes the concatenated KV.
+    path materializes the concatenated KV. compute_dtype as in flash_attention
+    (the fp8 pre-pass walks the chunks in place).
     """
     _check_kv_splits(kv_splits)
     b, lq, inner = q.shape
     n, _, l, _ = kv_chunks.shape
+    if _check_compute_dtype(compute_dtype, kv_splits, False):
+        q4 = q.view(b, lq, heads, dim_head).permute(0, 2, 1, 3)
+        k = kv_chunks[..., :inner].unflatten(-1, (heads, dim_head)).permute(1, 3, 0, 2, 4)
+        v = kv_chunks[..., inner:].unflatten(-1, (heads, dim_head)).permute(1, 3, 0, 2, 4)
+        return _flash_fp8(q4, k, v).transpose(1, 2).reshape(b, lq, inner)
     if use_hip(q):
         q4 = q.view(b, lq, heads, dim_head).permute(0, 2, 1, 3)
         k = kv_chunks[..., :inner].unflatten(-1, (heads, dim_head)).permute(1, 3, 0, 2, 4)

@@ -36,6 +36,60 @@ def flash_attention_lse(
     return out.to(q.dtype), lse
 
 
+_FP8_MAX = 448.0  # largest finite e4m3
+_FP8_P_SHIFT = 8  # p is quantised as e4m3(p * 2^8): 256 <= 448
+
+
+def fp8_block_exponent(amax: torch.Tensor) -> torch.Tensor:
+    """e = ceil(log2(amax / 448)) as int32: the power-of-two block scale 2^e
+    under which a block with that largest magnitude fills the e4m3 range. An
+    all-zero block has e = 0. Exact: 448 = 1.75 * 2^8, so e is the fp32
+    exponent of amax minus 8, one more when its significand exceeds 1.75 (the
+    integer add below carries into the exponent field). The E8M0 byte e + 127
+    is clamped to [1, 254]."""
+    bits = amax.float().contiguous().view(torch.int32)
+    byte = (((bits + 0x1FFFFF) >> 23) - 8).clamp(1, 254)
+    return torch.where(amax == 0, torch.zeros_like(byte), byte - 127)
+
+
+def _fp8_dequantised(x: torch.Tensor, e: torch.Tensor) -> torch.Tensor:
+    """e4m3(x * 2^-e) * 2^e in fp32; e broadcasts against x."""
+    xq = torch.ldexp(x.float(), -e).to(torch.float8_e4m3fn).float()
+    return torch.ldexp(xq, e)
+
+
+def fp8_attention_operands(q, k, v):
+    """The fp32 values the fp8 attention path multiplies: q with one scale per
+    row, k with one per token, v with one per (channel, block of 32 consecutive
+    tokens, the last block short). q: [B, H, Lq, D]; k, v: [B, H, Lkv, D]."""
+    qd = _fp8_dequantised(q, fp8_block_exponent(q.float().abs().amax(-1, keepdim=True)))
+    kd = _fp8_dequantised(k, fp8_block_exponent(k.float().abs().amax(-1, keepdim=True)))
+    lkv = v.shape[-2]
+    pad = -lkv % 32
+    vb = F.pad(v.float(), (0, 0, 0, pad)).unflatten(-2, (-1, 32))  # [B, H, blocks, 32, D]
+    vd = _fp8_dequantised(vb, fp8_block_exponent(vb.abs().amax(-2, keepdim=True)))
+    return qd, kd, vd.flatten(-3, -2)[..., :lkv, :]
+
+
+def flash_attention_fp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+    """Attention with e4m3 operands, the arithmetic of compute_dtype="fp8".
+
+    Every operand is x_hat = e4m3(x * 2^-e) with a power-of-two block scale,
+    e = fp8_block_exponent(amax of the block): q per row, k per token, v per
+    (channel, 32 tokens). Scores q_hat . k_hat, the row max, p = exp(s - max)
+    and the row sum l of p are fp32; p enters the second product as
+    e4m3(p * 2^8) * 2^-8; o = (p_hat @ v_hat) / l in fp32, rounded once to the
+    input dtype. q: [B, H, Lq, D]; k, v: [B, H, Lkv, D] -> [B, H, Lq, D].
+    """
+    qd, kd, vd = fp8_attention_operands(q, k, v)
+    s = torch.einsum("bhqd,bhkd->bhqk", qd, kd) * q.shape[-1] ** -0.5
+    p = torch.exp(s - s.amax(-1, keepdim=True))
+    l = p.sum(-1, keepdim=True)
+    ph = torch.ldexp(torch.ldexp(p, torch.tensor(_FP8_P_SHIFT)).to(torch.float8_e4m3fn).float(),
+                     torch.tensor(-_FP8_P_SHIFT))
+    return (torch.einsum("bhqk,bhkd->bhqd", ph, vd) / l).to(q.dtype)
+
+
 def merge_attention(
     o_parts: torch.Tensor, lse_parts: torch.Tensor, out_dtype: torch.dtype | None = None
 ) -> tuple[torch.Tensor, torch.Tensor]:

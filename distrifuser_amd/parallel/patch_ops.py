@@ -386,8 +386,12 @@ class PatchSelfAttention(nn.Module):
         q = q.view(b, lq, self.heads, self.dim_head).transpose(1, 2)
         k = k.view(b, lkv, self.heads, self.dim_head).transpose(1, 2)
         v = v.view(b, lkv, self.heads, self.dim_head).transpose(1, 2)
-        splits = self.state.config.attn_splits(b, self.heads, lq, lkv, self.dim_head)
-        out = ops.flash_attention(q, k, v, kv_splits=splits)
+        fp8 = self.state.config.attn_compute_dtype(self.dim_head)
+        if fp8 is None:
+            splits = self.state.config.attn_splits(b, self.heads, lq, lkv, self.dim_head)
+            out = ops.flash_attention(q, k, v, kv_splits=splits)
+        else:
+            out = ops.flash_attention(q, k, v, compute_dtype=fp8)
         return out.transpose(1, 2).reshape(b, lq, inner)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -434,10 +438,16 @@ class PatchSelfAttention(nn.Module):
         # The buffer view [n, B, L, 2C] IS the full displaced KV (peers are
         # ordered by patch index = full image row order); the kernel walks the
         # peer chunks in place — no torch.cat on the hot path.
-        splits = cfg.attn_splits(b, self.heads, l, cfg.n_device_per_batch * l, self.dim_head)
-        out = ops.flash_attention_chunked(
-            q, self._buffer_view, self.heads, self.dim_head, kv_splits=splits
-        )
+        fp8 = cfg.attn_compute_dtype(self.dim_head)
+        if fp8 is None:
+            splits = cfg.attn_splits(b, self.heads, l, cfg.n_device_per_batch * l, self.dim_head)
+            out = ops.flash_attention_chunked(
+                q, self._buffer_view, self.heads, self.dim_head, kv_splits=splits
+            )
+        else:
+            out = ops.flash_attention_chunked(
+                q, self._buffer_view, self.heads, self.dim_head, compute_dtype=fp8
+            )
         return self.to_out(out)
 
 

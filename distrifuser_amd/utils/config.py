@@ -53,6 +53,19 @@ def _parse_attn_kv_splits(value) -> int | str:
     return int(value)
 
 
+def _parse_attn_dtype(value) -> str | None:
+    """None or "fp8" (an empty or "none" string from the environment is None)."""
+    if value is None:
+        return None
+    if isinstance(value, str):
+        name = value.strip().lower()
+        if name in ("", "none"):
+            return None
+        if name == "fp8":
+            return "fp8"
+    raise ValueError(f"attn_dtype must be None or 'fp8', got {value!r}")
+
+
 def is_power_of_2(n: int) -> bool:
     return n >= 1 and (n & (n - 1)) == 0
 
@@ -90,6 +103,7 @@ class DistriConfig:
         backend: str | None = None,
         device: str | torch.device | None = None,
         attn_kv_splits: int | str = _ATTN_KV_SPLITS_UNSET,
+        attn_dtype: str | None = None,
     ):
         # Self-attention split-KV: a positive int, or "auto" for
         # ops.attention_kv_splits per call site. Left at its default (1), the
@@ -97,6 +111,12 @@ class DistriConfig:
         if attn_kv_splits is _ATTN_KV_SPLITS_UNSET:
             attn_kv_splits = os.environ.get("DFA_ATTN_KV_SPLITS") or 1
         self.attn_kv_splits = _parse_attn_kv_splits(attn_kv_splits)
+        # Self-attention arithmetic at head_dim 64: None (the 16-bit kernels) or
+        # "fp8" (e4m3 operands, ops.flash_attention(compute_dtype="fp8")). Left
+        # at None, the DFA_ATTN_DTYPE environment variable takes its place.
+        if attn_dtype is None:
+            attn_dtype = os.environ.get("DFA_ATTN_DTYPE")
+        self.attn_dtype = _parse_attn_dtype(attn_dtype)
         assert mode in VALID_MODES, f"mode must be one of {VALID_MODES}, got {mode!r}"
         assert parallelism in VALID_PARALLELISM, (
             f"parallelism must be one of {VALID_PARALLELISM}, got {parallelism!r}"
@@ -225,6 +245,11 @@ class DistriConfig:
 
             return attention_kv_splits(b, heads, lq, lkv, dim_head, self.device)
         return self.attn_kv_splits
+
+    def attn_compute_dtype(self, dim_head: int) -> str | None:
+        """compute_dtype for one self-attention call: the knob at head_dim 64
+        (the fp8 kernels' size), None for every other head dim."""
+        return self.attn_dtype if dim_head == 64 else None
 
     @property
     def use_patch_parallelism(self) -> bool:

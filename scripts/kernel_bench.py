@@ -3,7 +3,8 @@
 Run on an MI355X: python scripts/kernel_bench.py > gpurun_out/kernel_bench.json
 (--splitkv-only: just the split-KV attention sweep; --vae-downsample-only:
 just the VAE-encoder downsample convs; --rescale-only: just the rescaled
-DDIM step, native against the torch composition; --dtype {bf16,fp16}: the
+DDIM step, native against the torch composition; --fp8-only: the e4m3
+attention path against the 16-bit kernel; --dtype {bf16,fp16}: the
 element type of the attention, conv, LayerNorm and VAE-attention rows, default
 bf16 — fp16 rows carry "dtype": "fp16")
 """
@@ -74,6 +75,52 @@ def splitkv_sweep(results, reps=5, iters=100):
             t = sorted(ms[name])
             row[f"ms_{name}"] = t[len(t) // 2]
             row[f"spread_{name}"] = [t[0], t[-1]]
+        results.append(row)
+        print(json.dumps(row), flush=True)
+
+
+def fp8_attention_rows(results, dt, tag, reps=5, iters=30):
+    """compute_dtype="fp8" (KV pre-pass + kernel, and the pre-pass alone)
+    against the 16-bit kernel of the same build, head_dim 64: plain L = 3.6k,
+    14.4k, 57.6k and the two displaced-patch chunked shapes. Interleaved `reps`
+    times; median and min..max of the repeats, and the rel-L2 distance of the
+    two outputs."""
+    from distrifuser_amd import ops
+
+    dev = "cuda:0"
+    ext = ops.hip_ext()
+    shapes = [("plain", 20, 3600, 1), ("plain", 20, 14400, 1), ("plain", 10, 57600, 1),
+              ("chunked", 10, 7200, 8), ("chunked", 20, 3600, 4)]
+    for kind, h, lq, n in shapes:
+        lkv, inner = lq * n, h * 64
+        q = torch.randn(1, h, lq, 64, device=dev, dtype=dt)
+        if kind == "chunked":
+            slot = lq * 2 * inner
+            buf = torch.randn(n, slot + 64, device=dev, dtype=dt)
+            kv = buf[:, :slot].view(n, 1, lq, 2 * inner)
+            k = kv[..., :inner].unflatten(-1, (h, 64)).permute(1, 3, 0, 2, 4)
+            v = kv[..., inner:].unflatten(-1, (h, 64)).permute(1, 3, 0, 2, 4)
+        else:
+            k = torch.randn(1, h, lkv, 64, device=dev, dtype=dt)
+            v = torch.randn(1, h, lkv, 64, device=dev, dtype=dt)
+        fns = {"b16": lambda: ext.flash_attention(q, k, v),
+               "fp8": lambda: ext.flash_attention_fp8(q, k, v),
+               "fp8_prepass": lambda: ext.attn_quant_kv(q, k, v)}
+        a, b = fns["b16"]().float(), fns["fp8"]().float()
+        ms = {name: [] for name in fns}
+        for _ in range(reps):
+            for name, fn in fns.items():
+                ms[name].append(timeit(fn, iters=iters))
+        flops = 4.0 * h * lq * lkv * 64
+        row = {**tag, "op": "flash_attention_fp8", "kind": kind, "heads": h, "Lq": lq,
+               "Lkv": lkv, "n_chunks": n, "reps": reps,
+               "rel_l2_fp8_vs_b16": ((a - b).norm() / a.norm()).item()}
+        for name, t in ms.items():
+            t = sorted(t)
+            row[f"ms_{name}"] = t[len(t) // 2]
+            row[f"spread_{name}"] = [t[0], t[-1]]
+        row["tflops_b16"] = flops / row["ms_b16"] / 1e9
+        row["tflops_fp8"] = flops / row["ms_fp8"] / 1e9
         results.append(row)
         print(json.dumps(row), flush=True)
 
@@ -178,6 +225,10 @@ def main():
         splitkv_sweep(results)
         with open("kernel_bench_splitkv.json", "w") as f:
             json.dump(results, f, indent=1)
+        return 0
+
+    if "--fp8-only" in sys.argv[1:]:
+        fp8_attention_rows(results, dt, tag)
         return 0
 
     if "--rescale-only" in sys.argv[1:]:
