@@ -90,6 +90,59 @@ def flash_attention_fp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> to
     return (torch.einsum("bhqk,bhkd->bhqd", ph, vd) / l).to(q.dtype)
 
 
+_KMEAN_TILE = 128  # tokens per partial sum of the K mean
+
+
+def attention_k_mean(k: torch.Tensor) -> torch.Tensor:
+    """fp32 per-channel mean of k [B, H, Lkv, D] over its tokens -> [B, H, D].
+
+    Summation order (one a kernel can keep without atomics): each 128-token
+    tile is summed in token order starting from 0, then the tile sums are added
+    in tile order starting from 0; the total is divided by Lkv with one true
+    division."""
+    lkv = k.shape[-2]
+    kt = F.pad(k.float(), (0, 0, 0, -lkv % _KMEAN_TILE)).unflatten(-2, (-1, _KMEAN_TILE))
+    part = torch.zeros_like(kt[..., 0, :])  # [B, H, tiles, D]
+    for j in range(_KMEAN_TILE):
+        part = part + kt[..., j, :]
+    total = torch.zeros_like(part[..., 0, :])
+    for t in range(part.shape[-2]):
+        total = total + part[..., t, :]
+    return total / lkv
+
+
+def fp8_qk_attention_operands(q: torch.Tensor, k: torch.Tensor):
+    """The fp32 values the fp8_qk first product multiplies: q with one scale
+    per row (as fp8_attention_operands), k - attention_k_mean(k) with one scale
+    per token."""
+    qd = _fp8_dequantised(q, fp8_block_exponent(q.float().abs().amax(-1, keepdim=True)))
+    kc = k.float() - attention_k_mean(k).unsqueeze(-2)
+    return qd, _fp8_dequantised(kc, fp8_block_exponent(kc.abs().amax(-1, keepdim=True)))
+
+
+def flash_attention_fp8_qk(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+    """Attention with an e4m3 first product and a 16-bit second one. A rule
+    only: it has no kernel and no compute_dtype, because its accuracy did not
+    justify one (profiles/attention_fp8_qk_notes.md; tests/test_fp8_qk_attention.py
+    holds the figures that decided it).
+
+    k is centred on its per-channel mean over all tokens (attention_k_mean, in
+    its stated order): a shift softmax does not see, since it moves every score
+    of a row by the same q . mu. q_hat and k'_hat are e4m3 under power-of-two
+    scales, one per q row and one per token. Scores q_hat . k'_hat * D^-0.5,
+    the row max, p = exp(s - max) and the row sum l of p are fp32; p enters the
+    second product rounded to the input dtype, v as it is;
+    o = (p16 @ v) / l in fp32, rounded once to the input dtype.
+    q: [B, H, Lq, D]; k, v: [B, H, Lkv, D] -> [B, H, Lq, D].
+    """
+    qd, kd = fp8_qk_attention_operands(q, k)
+    s = torch.einsum("bhqd,bhkd->bhqk", qd, kd) * q.shape[-1] ** -0.5
+    p = torch.exp(s - s.amax(-1, keepdim=True))
+    l = p.sum(-1, keepdim=True)
+    p16 = p.to(q.dtype).float()
+    return (torch.einsum("bhqk,bhkd->bhqd", p16, v.float()) / l).to(q.dtype)
+
+
 def merge_attention(
     o_parts: torch.Tensor, lse_parts: torch.Tensor, out_dtype: torch.dtype | None = None
 ) -> tuple[torch.Tensor, torch.Tensor]:
