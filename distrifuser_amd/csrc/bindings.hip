@@ -188,20 +188,6 @@ at::Tensor geglu(const at::Tensor& h_) {
     return out;
 }
 
-// The guidance_rescale factor of a step, or null: one fp32 on the GPU, for a
-// [2,C,h,w] CFG pair and x [1,C,h,w] only
-const float* rescale_factor(const char* op, const c10::optional<at::Tensor>& factor,
-                            const at::Tensor& noise, const at::Tensor& x) {
-    if (!factor.has_value()) return nullptr;
-    TORCH_CHECK(factor->is_cuda() && factor->scalar_type() == at::kFloat && factor->numel() == 1,
-                op, ": factor must be one fp32 value on the GPU");
-    TORCH_CHECK(noise.dim() == 4 && noise.size(0) == 2 && noise.numel() == 2 * x.numel(), op,
-                ": a rescale factor needs the [2,C,h,w] CFG pair as noise");
-    TORCH_CHECK(x.dim() == 4 && x.size(0) == 1, op,
-                ": a rescale factor needs x [1,C,h,w] (one sample)");
-    return factor->data_ptr<float>();
-}
-
 // r = phi * std(nc) / std(nu + g*(nc - nu)) + (1 - phi) over the one sample of
 // the [2,C,h,w] CFG pair -> fp32 [1]; two launches, the same bits on every run
 at::Tensor guidance_rescale_factor(const at::Tensor& noise, double g, double phi) {
@@ -220,49 +206,86 @@ at::Tensor guidance_rescale_factor(const at::Tensor& noise, double g, double phi
     return factor;
 }
 
-// noise=(cn, seed, draw) of a stochastic step, or nothing: x' += cn * z with z
-// the Philox normal of (seed, draw, element index). The index is the element's
-// offset in the one sample, so x must be [1,C,h,w].
+// The inputs of a fused step, validated. p reads the contiguous copies held
+// here, so it is good for as long as the struct.
+// noise: the [2,C,h,w] CFG pair [uncond; cond], or (masked or noisy steps: the
+// plain kernels always read the cond half) one branch's output in x's shape,
+// p.noise_c then null. x: [1,C,h,w] wherever an element's offset in the one
+// sample is read: a blend, step noise, a factor.
+// blend: init and init_noise fp32 [1,C,h,w], mask fp32 with h*w elements.
+// factor: one fp32 on the GPU, CFG pair only.
+// step_noise = (cn, seed, draw): x' += cn * z with z the Philox normal of
+// (seed, draw, element index).
 using NoiseArg = std::optional<std::tuple<double, uint64_t, uint32_t>>;
-struct StepNoiseArg {
-    StepNoise value;
-    bool given;
-    const StepNoise* ptr() const { return given ? &value : nullptr; }
+struct BlendArg {
+    const at::Tensor &init, &init_noise, &mask;
+    double sa, sb;
 };
-StepNoiseArg step_noise(const char* op, const NoiseArg& noise, const at::Tensor& x) {
-    if (!noise.has_value()) return {{0.f, 0, 0}, false};
-    TORCH_CHECK(x.dim() == 4 && x.size(0) == 1, op,
+struct StepArgs {
+    at::Tensor n, x, init, init_noise, mask;
+    StepParams p;
+};
+StepArgs step_args(const char* op, const at::Tensor& noise, const at::Tensor& x, double g,
+                   double ca, double cb, const c10::optional<at::Tensor>& factor,
+                   const NoiseArg& znoise, const BlendArg* blend = nullptr) {
+    TORCH_CHECK(noise.is_cuda() && x.is_cuda() && noise.scalar_type() == x.scalar_type(), op,
+                ": noise and x must be CUDA tensors of one dtype");
+    const bool one_sample = x.dim() == 4 && x.size(0) == 1;
+    TORCH_CHECK(blend == nullptr || one_sample, op, ": x must be CUDA [1,C,h,w]");
+    TORCH_CHECK(!znoise.has_value() || one_sample, op,
                 ": a noisy step needs x [1,C,h,w] (one sample)");
-    return {{(float)std::get<0>(*noise), std::get<1>(*noise), std::get<2>(*noise)}, true};
+    const bool branch_ok = blend != nullptr || znoise.has_value();
+    const bool pair = noise.numel() == 2 * x.numel() &&
+                      (blend != nullptr || (noise.dim() >= 1 && noise.size(0) == 2));
+    TORCH_CHECK(pair || (branch_ok && noise.numel() == x.numel()), op,
+                ": noise must be the [2,C,h,w] CFG pair",
+                branch_ok ? " or the output [1,C,h,w] of one branch" : "");
+    StepArgs a{noise.contiguous(), x.contiguous()};
+    a.p = {a.n.data_ptr(), nullptr, a.x.data_ptr(), nullptr, (float)g, (float)ca, (float)cb,
+           a.x.numel()};
+    if (pair)
+        a.p.noise_c = reinterpret_cast<const char*>(a.n.data_ptr()) +
+                      a.x.numel() * a.n.element_size();
+    if (blend != nullptr) {
+        const int64_t hw = x.size(2) * x.size(3);
+        auto f32_on_gpu = [&](const at::Tensor& t, int64_t numel, const char* name) {
+            TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.numel() == numel, op,
+                        ": ", name, " must be CUDA fp32 with ", numel, " elements");
+            return t.contiguous();
+        };
+        a.init = f32_on_gpu(blend->init, x.numel(), "init");
+        a.init_noise = f32_on_gpu(blend->init_noise, x.numel(), "init_noise");
+        a.mask = f32_on_gpu(blend->mask, hw, "mask");
+        a.p.blend = MaskBlend{a.init.data_ptr<float>(), a.init_noise.data_ptr<float>(),
+                              a.mask.data_ptr<float>(), (float)blend->sa, (float)blend->sb, hw};
+    }
+    if (factor.has_value()) {
+        TORCH_CHECK(factor->is_cuda() && factor->scalar_type() == at::kFloat &&
+                        factor->numel() == 1,
+                    op, ": factor must be one fp32 value on the GPU");
+        TORCH_CHECK(noise.dim() == 4 && noise.size(0) == 2 && pair, op,
+                    ": a rescale factor needs the [2,C,h,w] CFG pair as noise");
+        TORCH_CHECK(one_sample, op, ": a rescale factor needs x [1,C,h,w] (one sample)");
+        a.p.factor = factor->data_ptr<float>();
+    }
+    if (znoise.has_value())
+        a.p.noise = StepNoise{(float)std::get<0>(*znoise), std::get<1>(*znoise),
+                              std::get<2>(*znoise)};
+    return a;
 }
 
-// The unmasked step ops take the [2,C,h,w] CFG pair, or with noise= also the
-// single-branch output in x's shape; -> the cond half, null without a pair
-const void* cond_half(const char* op, const at::Tensor& n, const at::Tensor& xc, bool noisy) {
-    TORCH_CHECK(n.is_cuda() && xc.is_cuda() && n.scalar_type() == xc.scalar_type(), op,
-                ": noise and x must be CUDA tensors of one dtype");
-    if (noisy && n.numel() == xc.numel()) return nullptr;
-    TORCH_CHECK(n.size(0) == 2 && xc.numel() * 2 == n.numel(), op,
-                ": noise must be the [2,C,h,w] CFG pair",
-                noisy ? " or, with noise=, the output [1,C,h,w] of one branch" : "");
-    return reinterpret_cast<const char*>(n.data_ptr()) + xc.numel() * n.element_size();
+// out = ca*x + cb*eps (+ cn*z), blended with the known region when a has a blend
+at::Tensor affine_step(StepArgs a) {
+    auto out = at::empty_like(a.x);
+    a.p.out = out.data_ptr();
+    launch_cfg_affine_step(a.p, dtype_of(a.x), cur_stream());
+    return out;
 }
 
 at::Tensor cfg_affine_step(const at::Tensor& noise, const at::Tensor& x, double g, double ca,
                            double cb, const c10::optional<at::Tensor>& factor,
                            const NoiseArg& znoise) {
-    // noise: [2, C, H, W] = [uncond; cond]; x: [1, C, H, W]; out = ca*x + cb*eps
-    TORCH_CHECK(noise.is_cuda() && noise.dim() >= 1);
-    auto n = noise.contiguous();
-    auto xc = x.contiguous();
-    const auto nz = step_noise("cfg_affine_step", znoise, x);
-    const void* nc = cond_half("cfg_affine_step", n, xc, nz.given);
-    const float* fp = rescale_factor("cfg_affine_step", factor, noise, x);
-    auto out = at::empty_like(xc);
-    launch_cfg_affine_step(n.data_ptr(), nc, xc.data_ptr(), out.data_ptr(), (float)g, (float)ca,
-                           (float)cb, xc.numel(), dtype_of(xc), cur_stream(), nullptr, fp,
-                           nz.ptr());
-    return out;
+    return affine_step(step_args("cfg_affine_step", noise, x, g, ca, cb, factor, znoise));
 }
 
 // fp32 [numel]: the normals of elements offset .. offset + numel - 1 of the
@@ -278,38 +301,6 @@ at::Tensor philox_normal(int64_t numel, uint64_t seed, uint32_t draw, int64_t of
     return out;
 }
 
-// The inputs of a masked (inpaint) step: x [1,C,h,w] and noise [2,C,h,w] (a
-// CFG pair) or [1,C,h,w] (no guidance), one dtype; init and init_noise fp32
-// [1,C,h,w], mask fp32 with h*w elements. The contiguous copies live as long
-// as the struct; nc is null without a CFG pair.
-struct MaskedStepArgs {
-    at::Tensor n, x, init, init_noise, mask;
-    const void* nc;
-    MaskBlend blend;
-};
-MaskedStepArgs masked_step_args(const char* op, const at::Tensor& noise, const at::Tensor& x,
-                                const at::Tensor& init, const at::Tensor& init_noise,
-                                const at::Tensor& mask, double sa, double sb) {
-    TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.size(0) == 1, op, ": x must be CUDA [1,C,h,w]");
-    TORCH_CHECK(noise.is_cuda() && noise.scalar_type() == x.scalar_type() &&
-                    (noise.numel() == x.numel() || noise.numel() == 2 * x.numel()),
-                op, ": noise must be [2,C,h,w] or [1,C,h,w] in x's dtype");
-    const int64_t hw = x.size(2) * x.size(3);
-    auto f32_on_gpu = [&](const at::Tensor& t, int64_t numel, const char* name) {
-        TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.numel() == numel, op, ": ",
-                    name, " must be CUDA fp32 with ", numel, " elements");
-        return t.contiguous();
-    };
-    MaskedStepArgs a{noise.contiguous(), x.contiguous(), f32_on_gpu(init, x.numel(), "init"),
-                     f32_on_gpu(init_noise, x.numel(), "init_noise"),
-                     f32_on_gpu(mask, hw, "mask"), nullptr, {}};
-    if (noise.numel() == 2 * x.numel())
-        a.nc = reinterpret_cast<const char*>(a.n.data_ptr()) + x.numel() * a.n.element_size();
-    a.blend = {a.init.data_ptr<float>(), a.init_noise.data_ptr<float>(),
-               a.mask.data_ptr<float>(), (float)sa, (float)sb, hw};
-    return a;
-}
-
 // cfg_affine_step (or the plain affine step when noise has batch 1), then
 // out = m*x' + (1 - m)*(sa*init + sb*init_noise), in one launch
 at::Tensor masked_affine_step(const at::Tensor& noise, const at::Tensor& x,
@@ -317,14 +308,9 @@ at::Tensor masked_affine_step(const at::Tensor& noise, const at::Tensor& x,
                               const at::Tensor& mask, double g, double ca, double cb, double sa,
                               double sb, const c10::optional<at::Tensor>& factor,
                               const NoiseArg& znoise) {
-    auto a = masked_step_args("masked_affine_step", noise, x, init, init_noise, mask, sa, sb);
-    const float* fp = rescale_factor("masked_affine_step", factor, noise, x);
-    const auto nz = step_noise("masked_affine_step", znoise, x);
-    auto out = at::empty_like(a.x);
-    launch_cfg_affine_step(a.n.data_ptr(), a.nc, a.x.data_ptr(), out.data_ptr(), (float)g,
-                           (float)ca, (float)cb, a.x.numel(), dtype_of(a.x), cur_stream(),
-                           &a.blend, fp, nz.ptr());
-    return out;
+    const BlendArg blend{init, init_noise, mask, sa, sb};
+    return affine_step(
+        step_args("masked_affine_step", noise, x, g, ca, cb, factor, znoise, &blend));
 }
 
 // [copies, 9, h, w] = [latents / scale (4), mask (1), masked-image latents (4)]
@@ -647,26 +633,24 @@ at::Tensor conv3x3(const at::Tensor& x, const at::Tensor& wp,
     return o;
 }
 
-// n / nc: the contiguous noise and its cond half (null: no CFG pair, masked
-// only); xc contiguous. -> (prev, x0 fp32)
-std::vector<at::Tensor> dpm_step(const at::Tensor& n, const void* nc, const at::Tensor& xc,
-                                 const c10::optional<at::Tensor>& x0_prev, double g, double ca,
-                                 double cb, double cc, double cx, double ce,
-                                 const MaskBlend* blend, const float* factor,
-                                 const StepNoise* noise) {
-    const void* pp = nullptr;
+// -> (prev, x0 fp32); prev alone takes a's noise and blend
+std::vector<at::Tensor> dpm_step(StepArgs a, const c10::optional<at::Tensor>& x0_prev, double cc,
+                                 double cx, double ce) {
     at::Tensor p;
     if (x0_prev.has_value()) {
         p = x0_prev->contiguous();
-        TORCH_CHECK(p.is_cuda() && p.numel() == xc.numel() && p.scalar_type() == at::kFloat,
+        TORCH_CHECK(p.is_cuda() && p.numel() == a.x.numel() && p.scalar_type() == at::kFloat,
                     "x0_prev must be the fp32 state from the previous cfg_dpm_step");
-        pp = p.data_ptr();
+        a.p.x0_prev = p.data_ptr<float>();
     }
-    auto out = at::empty_like(xc);
-    auto x0 = at::empty_like(xc, xc.options().dtype(at::kFloat));
-    launch_cfg_dpm_step(n.data_ptr(), nc, xc.data_ptr(), pp, out.data_ptr(), x0.data_ptr(),
-                        (float)g, (float)ca, (float)cb, (float)cc, (float)cx, (float)ce,
-                        xc.numel(), dtype_of(xc), cur_stream(), blend, factor, noise);
+    auto out = at::empty_like(a.x);
+    auto x0 = at::empty_like(a.x, a.x.options().dtype(at::kFloat));
+    a.p.out = out.data_ptr();
+    a.p.x0_out = x0.data_ptr<float>();
+    a.p.cc = (float)cc;
+    a.p.cx = (float)cx;
+    a.p.ce = (float)ce;
+    launch_cfg_dpm_step(a.p, dtype_of(a.x), cur_stream());
     return {out, x0};
 }
 
@@ -675,13 +659,8 @@ std::vector<at::Tensor> cfg_dpm_step(const at::Tensor& noise, const at::Tensor& 
                                      double ca, double cb, double cc, double cx, double ce,
                                      const c10::optional<at::Tensor>& factor,
                                      const NoiseArg& znoise) {
-    TORCH_CHECK(noise.is_cuda() && noise.dim() >= 1);
-    auto n = noise.contiguous();
-    auto xc = x.contiguous();
-    const auto nz = step_noise("cfg_dpm_step", znoise, x);
-    const void* nc = cond_half("cfg_dpm_step", n, xc, nz.given);
-    return dpm_step(n, nc, xc, x0_prev, g, ca, cb, cc, cx, ce, nullptr,
-                    rescale_factor("cfg_dpm_step", factor, noise, x), nz.ptr());
+    return dpm_step(step_args("cfg_dpm_step", noise, x, g, ca, cb, factor, znoise), x0_prev, cc,
+                    cx, ce);
 }
 
 // cfg_dpm_step with the inpaint blend on prev; x0 is the unmasked step's
@@ -692,10 +671,9 @@ std::vector<at::Tensor> masked_dpm_step(const at::Tensor& noise, const at::Tenso
                                         double cc, double cx, double ce, double sa, double sb,
                                         const c10::optional<at::Tensor>& factor,
                                         const NoiseArg& znoise) {
-    auto a = masked_step_args("masked_dpm_step", noise, x, init, init_noise, mask, sa, sb);
-    const auto nz = step_noise("masked_dpm_step", znoise, x);
-    return dpm_step(a.n, a.nc, a.x, x0_prev, g, ca, cb, cc, cx, ce, &a.blend,
-                    rescale_factor("masked_dpm_step", factor, noise, x), nz.ptr());
+    const BlendArg blend{init, init_noise, mask, sa, sb};
+    return dpm_step(step_args("masked_dpm_step", noise, x, g, ca, cb, factor, znoise, &blend),
+                    x0_prev, cc, cx, ce);
 }
 
 at::Tensor layer_norm(const at::Tensor& x_, const at::Tensor& w_, const at::Tensor& b_,

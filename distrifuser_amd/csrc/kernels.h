@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <optional>
 
 enum DfaDtype : int { DFA_BF16 = 0, DFA_F16 = 1, DFA_F32 = 2 };
 
@@ -94,21 +95,37 @@ void launch_guidance_rescale_factor(const void* noise_u, const void* noise_c, fl
                                     int64_t total, float* ws, float* factor, int dtype,
                                     hipStream_t stream);
 
-// ---- fused CFG + scheduler step (affine: out = ca*x + cb*eps) ---------------
-// blend != null: the masked step, total = C*hw; noise_c may then be null (no
-// CFG pair: eps = noise_u, g is not read). Its 16-byte path needs hw a
-// multiple of the vector width and 16-byte aligned pointers.
-// factor != null (one fp32 on the device, noise_c not null): eps is replaced
-// by round(factor[0] * eps) before the update. A factor of 1 gives the bits
-// of the call without one.
-// noise != null with cn != 0: out = fma(cn, z, x') before any blend, z indexed
-// by the element's offset in the one sample; noise_c may then be null as well.
-// cn == 0 runs the instantiation of the call without noise, except for the
-// call that has none (no pair, no blend), which then adds 0 * z.
-void launch_cfg_affine_step(const void* noise_u, const void* noise_c, const void* x, void* out,
-                            float g, float ca, float cb, int64_t total, int dtype,
-                            hipStream_t stream, const MaskBlend* blend = nullptr,
-                            const float* factor = nullptr, const StepNoise* noise = nullptr);
+// ---- fused CFG + scheduler step ----------------------------------------------
+// Affine: out = ca*x + cb*eps, eps = noise_u + g*(noise_c - noise_u).
+// DPM-Solver++(2M): out = ca*x + cb*eps + cc*x0_prev (x0_prev may be null), and
+// x0_out = cx*x + ce*eps, which sees neither noise nor blend.
+// blend: the masked step, total = C*hw; noise_c may then be null (no CFG pair:
+// eps = noise_u, g is not read). The affine step's 16-byte path then needs hw
+// a multiple of the vector width and 16-byte aligned pointers.
+// factor (one fp32 on the device, noise_c not null): eps is replaced by
+// round(factor[0] * eps) before the update, in out and x0_out alike. A factor
+// of 1 gives the bits of the call without one.
+// noise with cn != 0: out = fma(cn, z, out) after the x0_prev term and before
+// any blend, z indexed by the element's offset in the one sample; noise_c may
+// then be null as well. cn == 0 runs the instantiation of the call without
+// noise, except for the call that has none (no pair, no blend), which then
+// adds 0 * z.
+struct StepParams {
+    const void* noise_u;
+    const void* noise_c;
+    const void* x;
+    void* out;
+    float g, ca, cb;
+    int64_t total;
+    const float* x0_prev = nullptr;  // DPM alone, from here to ce
+    float* x0_out = nullptr;
+    float cc = 0.f, cx = 0.f, ce = 0.f;
+    std::optional<MaskBlend> blend;
+    const float* factor = nullptr;
+    std::optional<StepNoise> noise;
+};
+void launch_cfg_affine_step(const StepParams& p, int dtype, hipStream_t stream);
+void launch_cfg_dpm_step(const StepParams& p, int dtype, hipStream_t stream);
 
 // ---- inpaint U-Net input assembly --------------------------------------------
 // out [copies, 9, hw]: channels 0..3 = latents [4, hw] / scale, channel 4 =
@@ -147,18 +164,6 @@ struct Conv3x3Params {
 };
 // dtype: DFA_BF16 or DFA_F16 for x, halos, wp, bias, residual, bias2 and o alike
 void launch_conv3x3(const Conv3x3Params& p, int stride, int dtype, hipStream_t stream);
-
-// ---- fused CFG + DPM-Solver++(2M) step --------------------------------------
-// out = ca*x + cb*eps + cc*x0_prev (x0_prev may be null); x0_out = cx*x + ce*eps
-// blend != null: out is blended as in the masked affine step (nc may be null);
-// x0_out is not. factor as in the affine step: out and x0_out both use eps_r.
-// noise as in the affine step: added to out after the x0_prev term and before
-// the blend; x0_out never sees it.
-void launch_cfg_dpm_step(const void* nu, const void* nc, const void* x, const void* x0_prev,
-                         void* out, void* x0_out, float g, float ca, float cb, float cc,
-                         float cx, float ce, int64_t total, int dtype, hipStream_t stream,
-                         const MaskBlend* blend = nullptr, const float* factor = nullptr,
-                         const StepNoise* noise = nullptr);
 
 // ---- fused (residual +) LayerNorm (bf16 or fp16, C <= 2048, C % 8 == 0) -------------
 // y = LN(x [+ res]); when res != null and sum_out != null, x+res is also

@@ -197,47 +197,49 @@ __global__ void cfg_affine_step_kernel(const T* __restrict__ noise_u,
 
 bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
-// Whether a step takes its NOISE instantiation: cn != 0, or the one call that
-// has no instantiation without it (no CFG pair and no blend: the plain kernels
-// always read noise_c), which then adds 0 * z.
-bool step_draws(const StepNoise* noise, const void* noise_c, const MaskBlend* blend) {
-    return noise != nullptr && (noise->cn != 0.f || (noise_c == nullptr && blend == nullptr));
+PhiloxKey philox_key(const StepNoise& noise) {
+    return PhiloxKey{(uint32_t)noise.seed, (uint32_t)(noise.seed >> 32), noise.draw};
 }
 
-PhiloxKey philox_key(const StepNoise* noise) {
-    if (noise == nullptr) return PhiloxKey{0u, 0u, 0u};
-    return PhiloxKey{(uint32_t)noise->seed, (uint32_t)(noise->seed >> 32), noise->draw};
+// Whether a step takes its NOISE instantiation, and what that reads: cn != 0,
+// or the one call that has no instantiation without it (no CFG pair and no
+// blend: the plain kernels always read noise_c), which then adds 0 * z.
+struct StepDraw {
+    bool noisy;
+    float cn;
+    PhiloxKey key;
+};
+StepDraw step_draw(const StepParams& p) {
+    if (p.noise && (p.noise->cn != 0.f || (p.noise_c == nullptr && !p.blend)))
+        return {true, p.noise->cn, philox_key(*p.noise)};
+    return {false, 0.f, PhiloxKey{0u, 0u, 0u}};
 }
 
 }  // namespace
 
-void launch_cfg_affine_step(const void* noise_u, const void* noise_c, const void* x, void* out,
-                            float g, float ca, float cb, int64_t total, int dtype,
-                            hipStream_t stream, const MaskBlend* blend, const float* factor,
-                            const StepNoise* noise) {
+void launch_cfg_affine_step(const StepParams& p, int dtype, hipStream_t stream) {
     const int block = 256;
-    const bool noisy = step_draws(noise, noise_c, blend);
-    const float cn = noisy ? noise->cn : 0.f;
-    const PhiloxKey key = philox_key(noisy ? noise : nullptr);
+    const StepDraw d = step_draw(p);
     dispatch_dtype(dtype, [&]<typename T>(std::type_identity<T>) {
-        dispatch_bool(blend != nullptr, [&]<bool MASKED>(std::bool_constant<MASKED>) {
-            bool vec = total % VecN<T>::value == 0;
-            if (noisy)  // noise_c may be null: aligned16(nullptr) holds
-                vec = vec && aligned16(noise_u) && aligned16(noise_c) && aligned16(x) &&
-                      aligned16(out);
+        dispatch_bool(p.blend.has_value(), [&]<bool MASKED>(std::bool_constant<MASKED>) {
+            bool vec = p.total % VecN<T>::value == 0;
+            if (d.noisy)  // noise_c may be null: aligned16(nullptr) holds
+                vec = vec && aligned16(p.noise_u) && aligned16(p.noise_c) && aligned16(p.x) &&
+                      aligned16(p.out);
             if constexpr (MASKED)
-                vec = blend->hw % VecN<T>::value == 0 && aligned16(noise_u) &&
-                      aligned16(noise_c) && aligned16(x) && aligned16(out) &&
-                      aligned16(blend->init) && aligned16(blend->init_noise) &&
-                      aligned16(blend->mask);
+                vec = p.blend->hw % VecN<T>::value == 0 && aligned16(p.noise_u) &&
+                      aligned16(p.noise_c) && aligned16(p.x) && aligned16(p.out) &&
+                      aligned16(p.blend->init) && aligned16(p.blend->init_noise) &&
+                      aligned16(p.blend->mask);
             dispatch_bool(vec, [&]<bool VEC>(std::bool_constant<VEC>) {
-                dispatch_bool(factor != nullptr, [&]<bool RESCALE>(std::bool_constant<RESCALE>) {
-                    dispatch_bool(noisy, [&]<bool NOISE>(std::bool_constant<NOISE>) {
-                        const int grid = grid_for(total / (VEC ? VecN<T>::value : 1), block);
+                dispatch_bool(p.factor != nullptr, [&]<bool RESCALE>(std::bool_constant<RESCALE>) {
+                    dispatch_bool(d.noisy, [&]<bool NOISE>(std::bool_constant<NOISE>) {
+                        const int grid = grid_for(p.total / (VEC ? VecN<T>::value : 1), block);
                         cfg_affine_step_kernel<T, VEC, MASKED, RESCALE, NOISE>
                             <<<grid, block, 0, stream>>>(
-                                (const T*)noise_u, (const T*)noise_c, (const T*)x, (T*)out, g, ca,
-                                cb, total, MASKED ? *blend : MaskBlend{}, factor, cn, key);
+                                (const T*)p.noise_u, (const T*)p.noise_c, (const T*)p.x,
+                                (T*)p.out, p.g, p.ca, p.cb, p.total,
+                                p.blend.value_or(MaskBlend{}), p.factor, d.cn, d.key);
                     });
                 });
             });
@@ -290,23 +292,18 @@ __global__ void cfg_dpm_step_kernel(const T* __restrict__ noise_u, const T* __re
 
 }  // namespace
 
-void launch_cfg_dpm_step(const void* nu, const void* nc, const void* x, const void* x0_prev,
-                         void* out, void* x0_out, float g, float ca, float cb, float cc,
-                         float cx, float ce, int64_t total, int dtype, hipStream_t stream,
-                         const MaskBlend* blend, const float* factor, const StepNoise* noise) {
+void launch_cfg_dpm_step(const StepParams& p, int dtype, hipStream_t stream) {
     const int block = 256;
-    const int grid = grid_for(total, block);
-    const bool noisy = step_draws(noise, nc, blend);
-    const float cn = noisy ? noise->cn : 0.f;
-    const PhiloxKey key = philox_key(noisy ? noise : nullptr);
+    const int grid = grid_for(p.total, block);
+    const StepDraw d = step_draw(p);
     dispatch_dtype(dtype, [&]<typename T>(std::type_identity<T>) {
-        dispatch_bool(blend != nullptr, [&]<bool MASKED>(std::bool_constant<MASKED>) {
-            dispatch_bool(factor != nullptr, [&]<bool RESCALE>(std::bool_constant<RESCALE>) {
-                dispatch_bool(noisy, [&]<bool NOISE>(std::bool_constant<NOISE>) {
+        dispatch_bool(p.blend.has_value(), [&]<bool MASKED>(std::bool_constant<MASKED>) {
+            dispatch_bool(p.factor != nullptr, [&]<bool RESCALE>(std::bool_constant<RESCALE>) {
+                dispatch_bool(d.noisy, [&]<bool NOISE>(std::bool_constant<NOISE>) {
                     cfg_dpm_step_kernel<T, MASKED, RESCALE, NOISE><<<grid, block, 0, stream>>>(
-                        (const T*)nu, (const T*)nc, (const T*)x, (const float*)x0_prev, (T*)out,
-                        (float*)x0_out, g, ca, cb, cc, cx, ce, total,
-                        MASKED ? *blend : MaskBlend{}, factor, cn, key);
+                        (const T*)p.noise_u, (const T*)p.noise_c, (const T*)p.x, p.x0_prev,
+                        (T*)p.out, p.x0_out, p.g, p.ca, p.cb, p.cc, p.cx, p.ce, p.total,
+                        p.blend.value_or(MaskBlend{}), p.factor, d.cn, d.key);
                 });
             });
         });
@@ -339,9 +336,8 @@ void launch_philox_normal(float* out, int64_t numel, int64_t offset, uint64_t se
     if (numel <= 0) return;
     const int block = 256;
     const int64_t nblocks = ((offset + numel - 1) >> 2) - (offset >> 2) + 1;
-    const StepNoise noise{1.f, seed, draw};
-    philox_normal_kernel<<<grid_for(nblocks, block), block, 0, stream>>>(out, numel, offset,
-                                                                         nblocks, philox_key(&noise));
+    philox_normal_kernel<<<grid_for(nblocks, block), block, 0, stream>>>(
+        out, numel, offset, nblocks, philox_key(StepNoise{1.f, seed, draw}));
 }
 
 namespace {

@@ -339,15 +339,13 @@ def guidance_rescale_factor(noise: torch.Tensor, g: float, phi: float) -> torch.
     return eager.guidance_rescale_factor(noise, g, phi)
 
 
-def _with_factor(factor) -> tuple:
-    """The trailing arguments of a native step: none without a factor, so a
-    plain step makes the call it always made."""
-    return () if factor is None else (factor,)
-
-
-def _with_noise(step_noise) -> dict:
-    """The keyword of a noisy native step: none without noise, as _with_factor."""
-    return {} if step_noise is None else {"step_noise": step_noise}
+def _step_ops(x: torch.Tensor, *blend: torch.Tensor) -> tuple:
+    """(the module whose fused step ops serve x, *blend as those take it): the
+    extension for a GPU x in bf16, fp16 or fp32, with the blend's init,
+    init_noise and mask as fp32 on x's device; else the eager twins."""
+    if use_hip(x) and x.dtype in _BOUNDARY_DTYPES:
+        return hip_ext(), *(_f32(t, x) for t in blend)
+    return eager, *blend
 
 
 def philox_normal(numel: int, seed: int, draw: int, offset: int = 0, device=None) -> torch.Tensor:
@@ -373,21 +371,17 @@ def cfg_affine_step(noise, x, g, ca, cb, factor=None, step_noise=None):
     drawn inside the kernel; x must then be [1,C,h,w], and noise may also be
     one branch's output in x's shape (eps = noise, g not read). cn == 0 gives
     the bits of the call without step_noise."""
-    if use_hip(x) and x.dtype in _BOUNDARY_DTYPES:
-        return hip_ext().cfg_affine_step(noise, x, g, ca, cb, *_with_factor(factor),
-                                         **_with_noise(step_noise))
-    return eager.cfg_affine_step(noise, x, g, ca, cb, factor, step_noise)
+    (ops,) = _step_ops(x)
+    return ops.cfg_affine_step(noise, x, g, ca, cb, factor, step_noise)
 
 
 def cfg_dpm_step(noise, x, x0_prev, g, ca, cb, cc, cx, ce, factor=None, step_noise=None):
     """CFG combine + DPM-Solver++(2M) update in one launch on GPU ->
     (prev, x0 fp32): prev = ca*x + cb*eps + cc*x0_prev (+ cn*z), x0 = cx*x +
     ce*eps. step_noise as in cfg_affine_step; x0 never sees it."""
-    if use_hip(x) and x.dtype in _BOUNDARY_DTYPES:
-        prev, x0 = hip_ext().cfg_dpm_step(noise, x, x0_prev, g, ca, cb, cc, cx, ce,
-                                          *_with_factor(factor), **_with_noise(step_noise))
-        return prev, x0
-    return eager.cfg_dpm_step(noise, x, x0_prev, g, ca, cb, cc, cx, ce, factor, step_noise)
+    (ops,) = _step_ops(x)
+    prev, x0 = ops.cfg_dpm_step(noise, x, x0_prev, g, ca, cb, cc, cx, ce, factor, step_noise)
+    return prev, x0
 
 
 def masked_affine_step(noise, x, init, init_noise, mask, g, ca, cb, sa, sb, factor=None,
@@ -402,12 +396,9 @@ def masked_affine_step(noise, x, init, init_noise, mask, g, ca, cb, sa, sb, fact
     fp32 with h*w elements, shared by the channels. factor (from
     ``guidance_rescale_factor``, CFG pair only) scales eps first. step_noise
     as in cfg_affine_step."""
-    if use_hip(x) and x.dtype in _BOUNDARY_DTYPES:
-        return hip_ext().masked_affine_step(noise, x, _f32(init, x), _f32(init_noise, x),
-                                            _f32(mask, x), g, ca, cb, sa, sb,
-                                            *_with_factor(factor), **_with_noise(step_noise))
-    return eager.masked_affine_step(noise, x, init, init_noise, mask, g, ca, cb, sa, sb, factor,
-                                    step_noise)
+    ops, init, init_noise, mask = _step_ops(x, init, init_noise, mask)
+    return ops.masked_affine_step(noise, x, init, init_noise, mask, g, ca, cb, sa, sb, factor,
+                                  step_noise)
 
 
 def masked_dpm_step(noise, x, x0_prev, init, init_noise, mask, g, ca, cb, cc, cx, ce, sa, sb,
@@ -415,14 +406,10 @@ def masked_dpm_step(noise, x, x0_prev, init, init_noise, mask, g, ca, cb, cc, cx
     """Inpaint step of DPM-Solver++(2M): cfg_dpm_step with the blend of
     masked_affine_step on prev. Returns (prev, x0); x0 (fp32) is not blended.
     factor and step_noise as in masked_affine_step."""
-    if use_hip(x) and x.dtype in _BOUNDARY_DTYPES:
-        prev, x0 = hip_ext().masked_dpm_step(noise, x, x0_prev, _f32(init, x),
-                                             _f32(init_noise, x), _f32(mask, x), g, ca, cb, cc,
-                                             cx, ce, sa, sb, *_with_factor(factor),
-                                             **_with_noise(step_noise))
-        return prev, x0
-    return eager.masked_dpm_step(noise, x, x0_prev, init, init_noise, mask, g, ca, cb, cc, cx,
-                                 ce, sa, sb, factor, step_noise)
+    ops, init, init_noise, mask = _step_ops(x, init, init_noise, mask)
+    prev, x0 = ops.masked_dpm_step(noise, x, x0_prev, init, init_noise, mask, g, ca, cb, cc, cx,
+                                   ce, sa, sb, factor, step_noise)
+    return prev, x0
 
 
 def inpaint_unet_input(latents, mask, masked_latents, scale=1.0, copies=1):

@@ -395,23 +395,35 @@ def _add_step_noise(xp: torch.Tensor, x: torch.Tensor, noise) -> torch.Tensor:
     return xp + cn * z
 
 
-def cfg_affine_step(noise, x, g, ca, cb, factor=None, step_noise=None):
-    """x' = ca*x + cb*eps of a CFG pair, eps scaled by factor when given.
-    step_noise = (cn, seed, draw) adds cn * z (``philox_normal``); noise may
-    then also be one branch's output in x's shape (eps = noise)."""
+def _affine_xp(noise, x, g, ca, cb, factor, step_noise):
+    """fp32 x' = ca*x + cb*eps (+ cn*z) of the affine schedulers, not yet rounded."""
     xp = ca * x.float() + cb * _cfg_eps(noise, x, g, factor)
-    return _add_step_noise(xp, x, step_noise).to(x.dtype)
+    return _add_step_noise(xp, x, step_noise)
 
 
-def cfg_dpm_step(noise, x, x0_prev, g, ca, cb, cc, cx, ce, factor=None, step_noise=None):
-    """DPM-Solver++(2M) step of a CFG pair -> (prev, x0 fp32); eps scaled by
-    factor when given. step_noise as in cfg_affine_step: added to prev alone."""
+def _dpm_xp(noise, x, x0_prev, g, ca, cb, cc, cx, ce, factor, step_noise):
+    """fp32 (prev, x0) of DPM-Solver++(2M): prev = ca*x + cb*eps, then
+    + cc*x0_prev, then + cn*z, not yet rounded; x0 = cx*x + ce*eps."""
     eps = _cfg_eps(noise, x, g, factor)
     xf = x.float()
     prev = ca * xf + cb * eps
     if x0_prev is not None:
         prev = prev + cc * x0_prev.float()
-    return _add_step_noise(prev, x, step_noise).to(x.dtype), cx * xf + ce * eps
+    return _add_step_noise(prev, x, step_noise), cx * xf + ce * eps
+
+
+def cfg_affine_step(noise, x, g, ca, cb, factor=None, step_noise=None):
+    """x' = ca*x + cb*eps of a CFG pair, eps scaled by factor when given.
+    step_noise = (cn, seed, draw) adds cn * z (``philox_normal``); noise may
+    then also be one branch's output in x's shape (eps = noise)."""
+    return _affine_xp(noise, x, g, ca, cb, factor, step_noise).to(x.dtype)
+
+
+def cfg_dpm_step(noise, x, x0_prev, g, ca, cb, cc, cx, ce, factor=None, step_noise=None):
+    """DPM-Solver++(2M) step of a CFG pair -> (prev, x0 fp32); eps scaled by
+    factor when given. step_noise as in cfg_affine_step: added to prev alone."""
+    prev, x0 = _dpm_xp(noise, x, x0_prev, g, ca, cb, cc, cx, ce, factor, step_noise)
+    return prev.to(x.dtype), x0
 
 
 def masked_affine_step(noise, x, init, init_noise, mask, g, ca, cb, sa, sb, factor=None,
@@ -421,8 +433,7 @@ def masked_affine_step(noise, x, init, init_noise, mask, g, ca, cb, sa, sb, fact
     x [1,C,h,w]; init, init_noise fp32 [1,C,h,w]; mask h*w elements, shared by
     the channels. factor: the guidance_rescale factor, CFG pair only.
     step_noise = (cn, seed, draw) adds cn * z to x' before the blend."""
-    xp = ca * x.float() + cb * _cfg_eps(noise, x, g, factor)
-    xp = _add_step_noise(xp, x, step_noise)
+    xp = _affine_xp(noise, x, g, ca, cb, factor, step_noise)
     return _mask_blend(xp, x, init, init_noise, mask, sa, sb)
 
 
@@ -432,13 +443,8 @@ def masked_dpm_step(noise, x, x0_prev, init, init_noise, mask, g, ca, cb, cc, cx
     blended with the known region; x0 = cx*x + ce*eps (fp32) is the unmasked
     step's. Returns (prev, x0). factor: the guidance_rescale factor.
     step_noise as in masked_affine_step."""
-    eps = _cfg_eps(noise, x, g, factor)
-    xf = x.float()
-    prev = ca * xf + cb * eps
-    if x0_prev is not None:
-        prev = prev + cc * x0_prev.float()
-    prev = _add_step_noise(prev, x, step_noise)
-    return _mask_blend(prev, x, init, init_noise, mask, sa, sb), cx * xf + ce * eps
+    prev, x0 = _dpm_xp(noise, x, x0_prev, g, ca, cb, cc, cx, ce, factor, step_noise)
+    return _mask_blend(prev, x, init, init_noise, mask, sa, sb), x0
 
 
 def inpaint_unet_input(latents, mask, masked_latents, scale=1.0, copies=1):

@@ -58,8 +58,12 @@ class SchedulerBase:
     # constructor arguments (and config() keys) of one class alone: a
     # scheduler_config.json written by another class may hold them
     extra_config_keys: tuple[str, ...] = ()
+    multistep = False  # keeps an x0 history: the dpm step ops
     _noise_seed = 0
     _draw = 0  # steps taken since set_timesteps / set_begin_index
+    _step_index = 0
+    _x0_prev: torch.Tensor | None = None
+    _t_prev: int | None = None
 
     def __init__(
         self,
@@ -181,7 +185,67 @@ class SchedulerBase:
 
         return guidance_rescale_factor(noise, guidance_scale, guidance_rescale)
 
-    def _guided_step_eager(self, noise, timestep, sample, guidance_scale, factor):
+    # -- the step state, and the one route to the fused step kernels -----------------
+
+    def _reset_step_state(self) -> None:
+        """What ``set_timesteps`` and ``set_begin_index`` start from: no step
+        taken, no multistep history."""
+        self._draw = 0
+        self._step_index = 0
+        self._x0_prev = None
+        self._t_prev = None
+
+    def _advance(self, timestep, x0=None) -> None:
+        """The one place the step state moves (the draw counter aside, which
+        ``_take_draw`` moves), for the fused route and the eager ``step``
+        alike. x0: the fp32 x0 estimate a multistep solver keeps."""
+        self._step_index += 1
+        self._x0_prev = x0
+        self._t_prev = int(timestep)
+
+    def _fused_step(self, noise, timestep, sample, guidance_scale, factor=None, blend=None):
+        """One step through the fused op, the only caller of the step ops:
+        ``_affine_coeffs`` and ``_noise_coeff`` of the subclass (neither moves
+        any state), the draw, the op, then ``_advance``. noise is the
+        [uncond; cond] pair or one branch's output in sample's shape. factor:
+        the guidance_rescale factor. blend = (mask, init, init_noise) makes it
+        the inpaint step, with ``_known_coeffs`` read before the advance.
+        ``multistep``: ``_affine_coeffs`` is (first, coeffs), and the dpm ops
+        take x0_prev (None on a first-order step) and return (prev, x0)."""
+        from .. import ops
+
+        coeffs = self._affine_coeffs(timestep)
+        head = (noise, sample)
+        if self.multistep:
+            first, coeffs = coeffs
+            head += (None if first else self._x0_prev,)
+        tail = (factor, self._take_draw(self._noise_coeff(timestep)))
+        if blend is None:
+            op = ops.cfg_dpm_step if self.multistep else ops.cfg_affine_step
+        else:
+            op = ops.masked_dpm_step if self.multistep else ops.masked_affine_step
+            mask, init, init_noise = blend
+            head += (init, init_noise, mask)
+            tail = (*self._known_coeffs(timestep), *tail)
+        out = op(*head, guidance_scale, *coeffs, *tail)
+        out, x0 = out if self.multistep else (out, None)
+        self._advance(timestep, x0)
+        return out
+
+    def guided_step(self, noise: torch.Tensor, timestep, sample: torch.Tensor,
+                    guidance_scale: float, guidance_rescale: float = 0.0) -> torch.Tensor:
+        """CFG combine + scheduler update; noise is the [uncond; cond] pair.
+        On GPU this is ONE fused kernel (csrc/scheduler.hip): the step math
+        runs outside the captured graphs, so its torch-op launch overhead is
+        otherwise exposed every denoise step. Every sampler's update is affine
+        in (x, eps) (``_affine_coeffs``); a stochastic one adds no launch (the
+        kernel draws the noise). guidance_rescale > 0 adds the two launches of
+        the factor op in front. Elsewhere: the CFG combine, then ``step``."""
+        from ..ops import use_hip
+
+        factor = self._rescale_factor(noise, sample, guidance_scale, guidance_rescale)
+        if use_hip(sample):
+            return self._fused_step(noise, timestep, sample, guidance_scale, factor)
         from ..ops.eager import _cfg_eps
 
         return self.step(_cfg_eps(noise, sample, guidance_scale, factor), timestep, sample)
@@ -245,11 +309,8 @@ class SchedulerBase:
             raise ValueError("a stochastic scheduler steps one sample [1,C,h,w]")
         factor = self._rescale_factor(noise, sample, guidance_scale, guidance_rescale)
         if use_hip(sample):
-            if factor is None:
-                return self._masked_step_native(noise, timestep, sample, guidance_scale, mask,
-                                                init, init_noise)
-            return self._masked_step_native(noise, timestep, sample, guidance_scale, mask, init,
-                                            init_noise, factor)
+            return self._fused_step(noise, timestep, sample, guidance_scale, factor,
+                                    (mask, init, init_noise))
         from ..ops.eager import _cfg_eps
 
         t_next = self._next_timestep(timestep)  # before step() moves on
@@ -259,10 +320,6 @@ class SchedulerBase:
         known = init if t_next is None else self.add_noise(init, init_noise, t_next)
         m = mask.float().to(sample.device).reshape(1, 1, *sample.shape[2:])
         return (m * xp + (1.0 - m) * known).to(sample.dtype)
-
-    def _masked_step_native(self, noise, timestep, sample, guidance_scale, mask, init,
-                            init_noise, factor=None) -> torch.Tensor:
-        raise NotImplementedError
 
     def set_begin_index(self, t_start: int) -> None:
         """Start the schedule at index ``t_start`` of the list that
@@ -275,7 +332,7 @@ class SchedulerBase:
         if not 0 <= t_start < n:
             raise ValueError(f"t_start must be in [0, {n}), got {t_start}")
         self.timesteps = self.timesteps[t_start:]
-        self._draw = 0
+        self._reset_step_state()
 
 
 def img2img_start(num_inference_steps: int, strength: float) -> int:

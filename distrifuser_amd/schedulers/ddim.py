@@ -29,7 +29,7 @@ class DDIMScheduler(SchedulerBase):
         self.timesteps = self._spaced_timesteps(num_inference_steps)
         if device is not None:
             self.timesteps = self.timesteps.to(device)
-        self._draw = 0
+        self._reset_step_state()
 
     def _alphas(self, timestep):
         """(acp_t, acp_prev) of the step at ``timestep``, fp32 tensors."""
@@ -48,13 +48,11 @@ class DDIMScheduler(SchedulerBase):
         return self.eta * max(var, 0.0) ** 0.5
 
     def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor) -> torch.Tensor:
-        from ..ops import cfg_affine_step, use_hip
+        from ..ops import use_hip
 
         if self.stochastic and use_hip(sample):
             # no CFG pair: still the one fused launch, which draws the noise
-            ca, cb = self._affine_coeffs(timestep)
-            return cfg_affine_step(model_output, sample, 1.0, ca, cb,
-                                   step_noise=self._take_draw(self._noise_coeff(timestep)))
+            return self._fused_step(model_output, timestep, sample, 1.0)
         alpha_t, alpha_prev = self._alphas(timestep)
         sig = self._noise_coeff(timestep)
 
@@ -68,31 +66,8 @@ class DDIMScheduler(SchedulerBase):
             pred_x0 = (x - (1 - alpha_t).sqrt() * eps) / alpha_t.sqrt()
         direction = (1 - alpha_prev - sig * sig).clamp_min(0).sqrt() * eps
         prev = alpha_prev.sqrt() * pred_x0 + direction
+        self._advance(timestep)
         return self._add_noise_eager(prev, sig).to(sample.dtype)
-
-    def guided_step(self, noise: torch.Tensor, timestep, sample: torch.Tensor,
-                    guidance_scale: float, guidance_rescale: float = 0.0) -> torch.Tensor:
-        # CFG combine + DDIM update; noise is the [uncond; cond] pair. On GPU
-        # this is ONE fused kernel (csrc/scheduler.hip) - the step math runs
-        # outside the captured graphs, so its torch-op launch overhead is
-        # otherwise exposed every denoise step. guidance_rescale > 0 adds the
-        # two launches of the factor op in front of it; eta > 0 adds none (the
-        # kernel draws the noise).
-        from ..ops import hip_ext, use_hip
-        from ..ops.dispatch import _with_noise
-
-        factor = self._rescale_factor(noise, sample, guidance_scale, guidance_rescale)
-        if use_hip(noise):
-            ca, cb = self._affine_coeffs(timestep)
-            nkw = _with_noise(self._take_draw(self._noise_coeff(timestep)))
-            if factor is None:
-                return hip_ext().cfg_affine_step(noise, sample, guidance_scale, ca, cb, **nkw)
-            return hip_ext().cfg_affine_step(noise, sample, guidance_scale, ca, cb, factor, **nkw)
-        if factor is not None:
-            return self._guided_step_eager(noise, timestep, sample, guidance_scale, factor)
-        nu, nc = noise.float().chunk(2)
-        eps = nu + guidance_scale * (nc - nu)
-        return self.step(eps, timestep, sample)
 
     def _affine_coeffs(self, timestep) -> tuple[float, float]:
         # x' = sqrt(a_p) * (x - sqrt(1-a_t) eps)/sqrt(a_t) + sqrt(1-a_p-sig^2) eps
@@ -108,12 +83,3 @@ class DDIMScheduler(SchedulerBase):
         ca = (alpha_prev / alpha_t) ** 0.5
         cb = sp - ca * (1 - alpha_t) ** 0.5
         return ca, cb
-
-    def _masked_step_native(self, noise, timestep, sample, guidance_scale, mask, init,
-                            init_noise, factor=None) -> torch.Tensor:
-        from ..ops import masked_affine_step
-
-        ca, cb = self._affine_coeffs(timestep)
-        sa, sb = self._known_coeffs(timestep)
-        return masked_affine_step(noise, sample, init, init_noise, mask, guidance_scale, ca, cb,
-                                  sa, sb, factor, self._take_draw(self._noise_coeff(timestep)))

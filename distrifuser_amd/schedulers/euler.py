@@ -14,7 +14,6 @@ class EulerDiscreteScheduler(SchedulerBase):
         acp = self._finite_alphas_cumprod().double()
         self._sigmas_train = ((1 - acp) / acp).sqrt().numpy()
         self.sigmas: torch.Tensor | None = None
-        self._step_index = 0
 
     def set_timesteps(self, num_inference_steps: int, device=None) -> None:
         self.num_inference_steps = num_inference_steps
@@ -25,13 +24,11 @@ class EulerDiscreteScheduler(SchedulerBase):
         if device is not None:
             self.timesteps = self.timesteps.to(device)
         self.init_noise_sigma = float((self.sigmas.max() ** 2 + 1) ** 0.5)
-        self._step_index = 0
-        self._draw = 0
+        self._reset_step_state()
 
     def set_begin_index(self, t_start: int) -> None:
         super().set_begin_index(t_start)
         self.sigmas = self.sigmas[t_start:]  # sigmas[i] pairs with timesteps[i]
-        self._step_index = 0
 
     def add_noise(self, sample: torch.Tensor, noise: torch.Tensor, timestep) -> torch.Tensor:
         """sample + sigma_t * noise (init_noise_sigma is for pure noise only)."""
@@ -49,17 +46,17 @@ class EulerDiscreteScheduler(SchedulerBase):
         it then adds: (sigma_next, 0.0) here."""
         return self.sigmas[self._step_index + 1], 0.0
 
-    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor) -> torch.Tensor:
-        from ..ops import cfg_affine_step, use_hip
+    def _noise_coeff(self, timestep=None) -> float:
+        return self._target_sigma()[1]
 
-        sigma_next, cn = self._target_sigma()
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor) -> torch.Tensor:
+        from ..ops import use_hip
+
         if self.stochastic and use_hip(sample):
             # no CFG pair: still the one fused launch, which draws the noise
-            ca, cb = self._affine_coeffs()
-            self._step_index += 1
-            return cfg_affine_step(model_output, sample, 1.0, ca, cb,
-                                   step_noise=self._take_draw(cn))
-        sigma = self.sigmas[self._step_index].to(sample.device)
+            return self._fused_step(model_output, timestep, sample, 1.0)
+        sigma_next, cn = self._target_sigma()
+        sigma =self.sigmas[self._step_index].to(sample.device)
         sigma_next = sigma_next.to(sample.device)
         x = sample.float()
         eps = model_output.float()
@@ -69,30 +66,8 @@ class EulerDiscreteScheduler(SchedulerBase):
             eps = x * (sigma / (sigma**2 + 1)) + eps / (sigma**2 + 1) ** 0.5
         # epsilon prediction: derivative d = eps; x_{t+1} = x + d * (s_next - s)
         prev = x + eps * (sigma_next - sigma)
-        self._step_index += 1
+        self._advance(timestep)
         return self._add_noise_eager(prev, cn).to(sample.dtype)
-
-    def guided_step(self, noise: torch.Tensor, timestep, sample: torch.Tensor,
-                    guidance_scale: float, guidance_rescale: float = 0.0) -> torch.Tensor:
-        # CFG combine + Euler update in ONE fused kernel on GPU (the update is
-        # affine in (x, eps): ca = 1, cb = sigma_next - sigma); guidance_rescale
-        # > 0 adds the two launches of the factor op in front of it
-        from ..ops import hip_ext, use_hip
-        from ..ops.dispatch import _with_noise
-
-        factor = self._rescale_factor(noise, sample, guidance_scale, guidance_rescale)
-        if use_hip(noise):
-            ca, cb = self._affine_coeffs()
-            nkw = _with_noise(self._take_draw(self._target_sigma()[1]))
-            self._step_index += 1
-            if factor is None:
-                return hip_ext().cfg_affine_step(noise, sample, guidance_scale, ca, cb, **nkw)
-            return hip_ext().cfg_affine_step(noise, sample, guidance_scale, ca, cb, factor, **nkw)
-        if factor is not None:
-            return self._guided_step_eager(noise, timestep, sample, guidance_scale, factor)
-        nu, nc = noise.float().chunk(2)
-        eps = nu + guidance_scale * (nc - nu)
-        return self.step(eps, timestep, sample)
 
     def _affine_coeffs(self, timestep=None) -> tuple[float, float]:
         """(ca, cb) of x' = ca*x + cb*model_output at the current step index."""
@@ -112,14 +87,3 @@ class EulerDiscreteScheduler(SchedulerBase):
         # known = init + sigma_next * init_noise; sigma = 0 after the last step
         last = self._step_index + 1 >= len(self.timesteps)
         return 1.0, 0.0 if last else float(self.sigmas[self._step_index + 1])
-
-    def _masked_step_native(self, noise, timestep, sample, guidance_scale, mask, init,
-                            init_noise, factor=None) -> torch.Tensor:
-        from ..ops import masked_affine_step
-
-        sa, sb = self._known_coeffs(timestep)
-        ca, cb = self._affine_coeffs()
-        step_noise = self._take_draw(self._target_sigma()[1])
-        self._step_index += 1
-        return masked_affine_step(noise, sample, init, init_noise, mask, guidance_scale, ca, cb,
-                                  sa, sb, factor, step_noise)
