@@ -401,17 +401,6 @@ at::Tensor flash_out(FlashAttnLseParams& p, const at::Tensor& q) {
     return o;
 }
 
-// one split, no log-sum-exp: the plain kernel -> logical [B,H,Lq,D]
-at::Tensor flash_plain(FlashAttnLseParams p, const at::Tensor& q) {
-    auto o = flash_out(p, q);
-    launch_flash_attention(p, 1, dtype_of(q), cur_stream());
-    return o.permute({0, 2, 1, 3});
-}
-
-at::Tensor flash_attention(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v) {
-    return flash_plain({flash_params(q, k, v)}, q);
-}
-
 // FP8 pre-pass alone: the quantised KV records of (k, v), uint8
 // [B*H, tiles, ATTN_FP8_TILE_BYTES]. q supplies B, H and the dtype.
 at::Tensor attn_quant_kv_p(const FlashAttnParams& p, const at::Tensor& q) {
@@ -525,27 +514,27 @@ std::vector<at::Tensor> flash_attention_ext(const at::Tensor& q, const at::Tenso
                                             bool return_lse) {
     auto [p, S, o_shape, lse_shape] = split_kv(q, k, v, kv_splits);
     const auto f32 = q.options().dtype(at::kFloat);
-    const long B = p.B, H = p.H, Lq = p.Lq;
-    if (S == 1) {
-        if (!return_lse) return {flash_plain(p, q)};
-        auto o = flash_out(p, q);
-        auto lse = at::empty({B, H, Lq}, f32);
-        p.lse = lse.data_ptr<float>();
+    c10::optional<at::Tensor> lse;
+    if (return_lse) lse = at::empty({(long)p.B, (long)p.H, (long)p.Lq}, f32);
+    at::Tensor o;
+    if (S == 1) {  // the kernel writes O and the lse themselves
+        o = flash_out(p, q);
+        if (return_lse) p.lse = lse->data_ptr<float>();
         launch_flash_attention(p, 1, dtype_of(q), cur_stream());
-        return {o.permute({0, 2, 1, 3}), lse};
+    } else {  // fp32 partials, then the merge writes both, O in the input dtype
+        auto o_part = at::empty(o_shape, f32);
+        auto lse_part = at::empty(lse_shape, f32);
+        p.o_part = o_part.data_ptr<float>();
+        p.lse = lse_part.data_ptr<float>();
+        launch_flash_attention(p, S, dtype_of(q), cur_stream());
+        o = merge_attention_into(o_part, lse_part, q.scalar_type(), lse);
     }
-    auto o_part = at::empty(o_shape, f32);
-    auto lse_part = at::empty(lse_shape, f32);
-    p.o_part = o_part.data_ptr<float>();
-    p.lse = lse_part.data_ptr<float>();
-    launch_flash_attention(p, S, dtype_of(q), cur_stream());
-    // the merge writes the input dtype
-    if (!return_lse)
-        return {merge_attention_into(o_part, lse_part, q.scalar_type(), c10::nullopt)
-                    .permute({0, 2, 1, 3})};
-    auto lse = at::empty({B, H, Lq}, f32);
-    auto o = merge_attention_into(o_part, lse_part, q.scalar_type(), lse);
-    return {o.permute({0, 2, 1, 3}), lse};
+    o = o.permute({0, 2, 1, 3});
+    return return_lse ? std::vector<at::Tensor>{o, *lse} : std::vector<at::Tensor>{o};
+}
+
+at::Tensor flash_attention(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v) {
+    return flash_attention_ext(q, k, v, 1, false)[0];
 }
 
 at::Tensor conv3x3(const at::Tensor& x, const at::Tensor& wp,

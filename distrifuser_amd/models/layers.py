@@ -40,22 +40,12 @@ class PlainSelfAttention(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         b, l, _ = x.shape
-        inner = self.heads * self.dim_head
-        q = self.to_q(x).view(b, l, self.heads, self.dim_head).transpose(1, 2)
-        k, v = self.to_kv(x).split(inner, dim=-1)
-        k = k.view(b, l, self.heads, self.dim_head).transpose(1, 2)
-        v = v.view(b, l, self.heads, self.dim_head).transpose(1, 2)
-        splits, fp8 = 1, None
+        q = ops.split_heads(self.to_q(x), self.heads)
+        k, v = (ops.split_heads(t, self.heads) for t in self.to_kv(x).chunk(2, dim=-1))
+        knobs = {}
         if self.config is not None:
-            fp8 = self.config.attn_compute_dtype(self.dim_head)
-            if fp8 is None:
-                splits = self.config.attn_splits(b, self.heads, l, l, self.dim_head)
-        if fp8 is None:
-            out = ops.flash_attention(q, k, v, kv_splits=splits)
-        else:
-            out = ops.flash_attention(q, k, v, compute_dtype=fp8)
-        out = out.transpose(1, 2).reshape(b, l, inner)
-        return self.to_out(out)
+            knobs = self.config.attn_kwargs(b, self.heads, l, l, self.dim_head)
+        return self.to_out(ops.merge_heads(ops.flash_attention(q, k, v, **knobs)))
 
 
 class PlainCrossAttention(nn.Module):
@@ -68,15 +58,10 @@ class PlainCrossAttention(nn.Module):
         self.to_out = nn.Linear(inner, query_dim, bias=out_bias)
 
     def forward(self, x: torch.Tensor, encoder_hidden_states: torch.Tensor) -> torch.Tensor:
-        b, lq, _ = x.shape
-        inner = self.heads * self.dim_head
-        lkv = encoder_hidden_states.shape[1]
-        q = self.to_q(x).view(b, lq, self.heads, self.dim_head).transpose(1, 2)
-        k, v = self.to_kv(encoder_hidden_states).split(inner, dim=-1)
-        k = k.view(b, lkv, self.heads, self.dim_head).transpose(1, 2)
-        v = v.view(b, lkv, self.heads, self.dim_head).transpose(1, 2)
-        out = ops.flash_attention(q, k, v).transpose(1, 2).reshape(b, lq, inner)
-        return self.to_out(out)
+        q = ops.split_heads(self.to_q(x), self.heads)
+        kv = self.to_kv(encoder_hidden_states)
+        k, v = (ops.split_heads(t, self.heads) for t in kv.chunk(2, dim=-1))
+        return self.to_out(ops.merge_heads(ops.flash_attention(q, k, v)))
 
 
 class FeedForward(nn.Module):

@@ -27,7 +27,9 @@ from .dispatch import (
     masked_affine_step,
     masked_dpm_step,
     merge_attention,
+    merge_heads,
     philox_normal,
+    split_heads,
     tokens_add_nchw,
     use_hip,
     vae_attention,
@@ -56,8 +58,10 @@ __all__ = [
     "masked_affine_step",
     "masked_dpm_step",
     "merge_attention",
+    "merge_heads",
     "pack_conv3x3_weight",
     "philox_normal",
+    "split_heads",
     "tokens_add_nchw",
     "use_hip",
     "vae_attention",

@@ -89,13 +89,39 @@ def _check_compute_dtype(compute_dtype, kv_splits: int, return_lse: bool) -> boo
     return True
 
 
-def _flash_fp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
-    """q [B,H,Lq,D], k/v [B,H,Lkv,D] or chunked [B,H,NC,LC,D] -> [B,H,Lq,D]."""
-    if use_hip(q) and _flash_ok(q, k, v) and q.shape[-1] == 64:
+def split_heads(x: torch.Tensor, heads: int) -> torch.Tensor:
+    """[B, L, heads*D] -> [B, heads, L, D], a view: x may be a column slice of
+    a fused projection, and the attention kernels read it in place."""
+    b, l, inner = x.shape
+    return x.view(b, l, heads, inner // heads).transpose(1, 2)
+
+
+def merge_heads(x: torch.Tensor) -> torch.Tensor:
+    """[B, H, L, D] -> [B, L, H*D]: the inverse of split_heads. A view of the
+    kernels' output, which is [B, L, H, D] in memory."""
+    b, h, l, d = x.shape
+    return x.transpose(1, 2).reshape(b, l, h * d)
+
+
+def _chunk_views(q: torch.Tensor, kv_chunks: torch.Tensor, heads: int):
+    """q [B,Lq,inner], kv_chunks [n,B,L,2*inner] -> q [B,H,Lq,D] and k, v
+    [B,H,n,L,D], all views: k and v are the two column halves of the buffer."""
+    k, v = (t.unflatten(-1, (heads, -1)).permute(1, 3, 0, 2, 4) for t in kv_chunks.chunk(2, dim=-1))
+    return split_heads(q, heads), k, v
+
+
+def _flash_native(q, k, v, kv_splits: int, return_lse: bool, fp8: bool):
+    """The result of the extension entry that serves this call (q [B,H,Lq,D],
+    k/v [B,H,Lkv,D] or chunked [B,H,NC,LC,D]), or None where none does: CPU,
+    DFA_FORCE_EAGER=1, what _flash_ok refuses, fp8 off head_dim 64."""
+    if not (use_hip(q) and _flash_ok(q, k, v)) or (fp8 and q.shape[-1] != 64):
+        return None
+    if fp8:
         return hip_ext().flash_attention_fp8(q, k, v)
-    if k.dim() == 5:
-        k, v = k.flatten(2, 3), v.flatten(2, 3)
-    return eager.flash_attention_fp8(q, k, v)
+    if kv_splits == 1 and not return_lse:
+        return hip_ext().flash_attention(q, k, v)
+    res = hip_ext().flash_attention_ext(q, k, v, kv_splits, return_lse)
+    return (res[0], res[1]) if return_lse else res[0]
 
 
 def flash_attention(
@@ -124,13 +150,14 @@ def flash_attention(
     kv_splits > 1 or return_lse.
     """
     _check_kv_splits(kv_splits)
-    if _check_compute_dtype(compute_dtype, kv_splits, return_lse):
-        return _flash_fp8(q, k, v)
-    if use_hip(q) and _flash_ok(q, k, v):
-        if kv_splits == 1 and not return_lse:
-            return hip_ext().flash_attention(q, k, v)
-        res = hip_ext().flash_attention_ext(q, k, v, kv_splits, return_lse)
-        return (res[0], res[1]) if return_lse else res[0]
+    fp8 = _check_compute_dtype(compute_dtype, kv_splits, return_lse)
+    out = _flash_native(q, k, v, kv_splits, return_lse, fp8)
+    if out is not None:
+        return out
+    if fp8:
+        if k.dim() == 5:
+            k, v = k.flatten(2, 3), v.flatten(2, 3)
+        return eager.flash_attention_fp8(q, k, v)
     # CPU, or fp32 / odd head-dims on GPU (PyTorch's SDPA, rocm AOTriton path)
     if return_lse:
         return eager.flash_attention_lse(q, k, v)
@@ -149,30 +176,17 @@ def flash_attention_chunked(
     (the fp8 pre-pass walks the chunks in place).
     """
     _check_kv_splits(kv_splits)
-    b, lq, inner = q.shape
-    n, _, l, _ = kv_chunks.shape
-    if _check_compute_dtype(compute_dtype, kv_splits, False):
-        q4 = q.view(b, lq, heads, dim_head).permute(0, 2, 1, 3)
-        k = kv_chunks[..., :inner].unflatten(-1, (heads, dim_head)).permute(1, 3, 0, 2, 4)
-        v = kv_chunks[..., inner:].unflatten(-1, (heads, dim_head)).permute(1, 3, 0, 2, 4)
-        return _flash_fp8(q4, k, v).transpose(1, 2).reshape(b, lq, inner)
-    if use_hip(q):
-        q4 = q.view(b, lq, heads, dim_head).permute(0, 2, 1, 3)
-        k = kv_chunks[..., :inner].unflatten(-1, (heads, dim_head)).permute(1, 3, 0, 2, 4)
-        v = kv_chunks[..., inner:].unflatten(-1, (heads, dim_head)).permute(1, 3, 0, 2, 4)
-        if _flash_ok(q4, k, v):
-            if kv_splits == 1:
-                o = hip_ext().flash_attention(q4, k, v)  # [B,H,Lq,D] (view of B,Lq,H,D)
-            else:
-                o = hip_ext().flash_attention_ext(q4, k, v, kv_splits, False)[0]
-            return o.transpose(1, 2).reshape(b, lq, inner)
-    full_kv = kv_chunks.permute(1, 0, 2, 3).reshape(b, n * l, 2 * inner)
-    k, v = full_kv.split(inner, dim=-1)
-    q4 = q.view(b, lq, heads, dim_head).transpose(1, 2)
-    k = k.view(b, n * l, heads, dim_head).transpose(1, 2)
-    v = v.view(b, n * l, heads, dim_head).transpose(1, 2)
-    out = flash_attention(q4, k.contiguous(), v.contiguous(), kv_splits=kv_splits)
-    return out.transpose(1, 2).reshape(b, lq, inner)
+    fp8 = _check_compute_dtype(compute_dtype, kv_splits, False)
+    q4, k, v = _chunk_views(q, kv_chunks, heads)
+    out = _flash_native(q4, k, v, kv_splits, False, fp8)
+    if out is None and fp8:
+        out = eager.flash_attention_fp8(q4, k.flatten(2, 3), v.flatten(2, 3))
+    elif out is None:
+        n, b, l, _ = kv_chunks.shape
+        full_kv = kv_chunks.permute(1, 0, 2, 3).reshape(b, n * l, -1)
+        k, v = (split_heads(t, heads).contiguous() for t in full_kv.chunk(2, dim=-1))
+        out = flash_attention(q4, k, v, kv_splits=kv_splits)  # may still reach the kernel
+    return merge_heads(out)
 
 
 def merge_attention(
@@ -202,7 +216,7 @@ def merge_attention(
         and o_parts.is_contiguous()
         and lse_parts.is_contiguous()
     ):
-        out, lse = hip_ext().merge_attention(o_parts, lse_parts, dt == torch.bfloat16, dt)
+        out, lse = hip_ext().merge_attention(o_parts, lse_parts, out_dtype=dt)
     else:
         out, lse = eager.merge_attention(o_parts, lse_parts, dt)
     return (out, lse) if return_lse else out

@@ -380,19 +380,10 @@ class PatchSelfAttention(nn.Module):
 
     def _attention(self, q: torch.Tensor, kv: torch.Tensor) -> torch.Tensor:
         """q: [B, Lq, inner]; kv: [B, Lkv, 2*inner] (may be strided)."""
-        b, lq, inner = q.shape
-        lkv = kv.shape[1]
-        k, v = kv.split(inner, dim=-1)
-        q = q.view(b, lq, self.heads, self.dim_head).transpose(1, 2)
-        k = k.view(b, lkv, self.heads, self.dim_head).transpose(1, 2)
-        v = v.view(b, lkv, self.heads, self.dim_head).transpose(1, 2)
-        fp8 = self.state.config.attn_compute_dtype(self.dim_head)
-        if fp8 is None:
-            splits = self.state.config.attn_splits(b, self.heads, lq, lkv, self.dim_head)
-            out = ops.flash_attention(q, k, v, kv_splits=splits)
-        else:
-            out = ops.flash_attention(q, k, v, compute_dtype=fp8)
-        return out.transpose(1, 2).reshape(b, lq, inner)
+        b, lq, _ = q.shape
+        knobs = self.state.config.attn_kwargs(b, self.heads, lq, kv.shape[1], self.dim_head)
+        q, k, v = (ops.split_heads(t, self.heads) for t in (q, *kv.chunk(2, dim=-1)))
+        return ops.merge_heads(ops.flash_attention(q, k, v, **knobs))
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         state = self.state
@@ -438,16 +429,8 @@ class PatchSelfAttention(nn.Module):
         # The buffer view [n, B, L, 2C] IS the full displaced KV (peers are
         # ordered by patch index = full image row order); the kernel walks the
         # peer chunks in place — no torch.cat on the hot path.
-        fp8 = cfg.attn_compute_dtype(self.dim_head)
-        if fp8 is None:
-            splits = cfg.attn_splits(b, self.heads, l, cfg.n_device_per_batch * l, self.dim_head)
-            out = ops.flash_attention_chunked(
-                q, self._buffer_view, self.heads, self.dim_head, kv_splits=splits
-            )
-        else:
-            out = ops.flash_attention_chunked(
-                q, self._buffer_view, self.heads, self.dim_head, compute_dtype=fp8
-            )
+        knobs = cfg.attn_kwargs(b, self.heads, l, cfg.n_device_per_batch * l, self.dim_head)
+        out = ops.flash_attention_chunked(q, self._buffer_view, self.heads, self.dim_head, **knobs)
         return self.to_out(out)
 
 
@@ -483,15 +466,8 @@ class CachedCrossAttention(nn.Module):
         self.kv_cache = None
 
     def forward(self, x: torch.Tensor, encoder_hidden_states: torch.Tensor) -> torch.Tensor:
-        b, lq, _ = x.shape
         if self.state.counter == 0 or self.kv_cache is None:
             self.kv_cache = self.to_kv(encoder_hidden_states)
-        kv = self.kv_cache
-        inner = self.heads * self.dim_head
-        k, v = kv.split(inner, dim=-1)
-        lkv = kv.shape[1]
-        q = self.to_q(x).view(b, lq, self.heads, self.dim_head).transpose(1, 2)
-        k = k.view(b, lkv, self.heads, self.dim_head).transpose(1, 2)
-        v = v.view(b, lkv, self.heads, self.dim_head).transpose(1, 2)
-        out = ops.flash_attention(q, k, v).transpose(1, 2).reshape(b, lq, inner)
-        return self.to_out(out)
+        q = ops.split_heads(self.to_q(x), self.heads)
+        k, v = (ops.split_heads(t, self.heads) for t in self.kv_cache.chunk(2, dim=-1))
+        return self.to_out(ops.merge_heads(ops.flash_attention(q, k, v)))

@@ -96,11 +96,9 @@ class TPAttention(nn.Module):
         if self.h_count:
             from .. import ops
 
-            q = self.to_q(x).view(b, l, self.h_count, self.dim_head).transpose(1, 2)
-            k = self.to_k(ctx).view(b, ctx.shape[1], self.h_count, self.dim_head).transpose(1, 2)
-            v = self.to_v(ctx).view(b, ctx.shape[1], self.h_count, self.dim_head).transpose(1, 2)
-            out = ops.flash_attention(q, k, v)
-            out = out.transpose(1, 2).reshape(b, l, self.h_count * self.dim_head)
+            q, k, v = (ops.split_heads(t, self.h_count)
+                       for t in (self.to_q(x), self.to_k(ctx), self.to_v(ctx)))
+            out = ops.merge_heads(ops.flash_attention(q, k, v))
             out = F.linear(out, self.to_out_weight)  # bias deferred past the reduce
         else:
             out = x.new_zeros(b, l, self.query_dim)

@@ -251,6 +251,15 @@ class DistriConfig:
         (the fp8 kernels' size), None for every other head dim."""
         return self.attn_dtype if dim_head == 64 else None
 
+    def attn_kwargs(self, b: int, heads: int, lq: int, lkv: int, dim_head: int) -> dict:
+        """The knob keywords of one self-attention call, for ops.flash_attention
+        and ops.flash_attention_chunked: fp8 where it applies, else the split
+        count (fp8 has no split-KV mode, so the count is not worked out then)."""
+        fp8 = self.attn_compute_dtype(dim_head)
+        if fp8 is not None:
+            return {"compute_dtype": fp8}
+        return {"kv_splits": self.attn_splits(b, heads, lq, lkv, dim_head)}
+
     @property
     def use_patch_parallelism(self) -> bool:
         return self.parallelism == "patch" and self.n_device_per_batch > 1
