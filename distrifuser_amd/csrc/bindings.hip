@@ -188,6 +188,50 @@ at::Tensor geglu(const at::Tensor& h_) {
     return out;
 }
 
+// x [..., K] (contiguous, or 2-D with contiguous rows) x packed [2*inner, K]
+// (ops.pack_geglu_weight) + bias [2*inner] -> a * gelu(gate) [..., inner]
+at::Tensor geglu_linear(const at::Tensor& x, const at::Tensor& packed, const at::Tensor& bias_,
+                        int64_t inner) {
+    TORCH_CHECK(x.is_cuda() && is_b16(x) && x.dim() >= 1, "geglu_linear: CUDA bf16 or fp16 x");
+    const int64_t K = x.size(-1);
+    TORCH_CHECK(K >= 8 && K % 8 == 0 && inner >= 8 && inner % 8 == 0,
+                "geglu_linear: K and inner must be positive multiples of 8, got ", K, ", ", inner);
+    int64_t ld = K;
+    if (x.dim() == 2 && x.size(0) > 1 && !x.is_contiguous()) {
+        ld = x.stride(0);
+        TORCH_CHECK(x.stride(1) == 1 && ld >= K && ld % 8 == 0,
+                    "geglu_linear: rows must be contiguous and a multiple of 8 elements apart");
+    } else {
+        TORCH_CHECK(x.is_contiguous(), "geglu_linear: x must be contiguous");
+    }
+    TORCH_CHECK(ld < (int64_t(1) << 22), "geglu_linear: row stride too large");
+    TORCH_CHECK(packed.is_cuda() && packed.scalar_type() == x.scalar_type() &&
+                    packed.is_contiguous() &&
+                    packed.numel() == geglu_linear_packed_numel((int)K, (int)inner),
+                "geglu_linear: packed must be pack_geglu_weight's result for [", 2 * inner, ", ",
+                K, "] in x's dtype");
+    TORCH_CHECK(bias_.numel() == 2 * inner, "geglu_linear: bias must have ", 2 * inner,
+                " elements");
+    auto bias = b16_param(bias_, x, "geglu_linear", "bias");
+    auto sizes = x.sizes().vec();
+    sizes.back() = inner;
+    auto out = at::empty(sizes, x.options());
+    const auto addr = [](const at::Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()); };
+    TORCH_CHECK(addr(x) % 16 == 0 && addr(packed) % 16 == 0 && addr(bias) % 8 == 0,
+                "geglu_linear: x and packed must be 16-byte aligned, bias 8-byte aligned");
+    GegluLinearParams p{};
+    p.x = reinterpret_cast<const uint16_t*>(x.data_ptr());
+    p.wp = reinterpret_cast<const uint16_t*>(packed.data_ptr());
+    p.bias = reinterpret_cast<const uint16_t*>(bias.data_ptr());
+    p.out = reinterpret_cast<uint16_t*>(out.data_ptr());
+    p.rows = x.numel() / K;
+    p.ld = ld;
+    p.K = (int)K;
+    p.inner = (int)inner;
+    launch_geglu_linear(p, dtype_of(x), cur_stream());
+    return out;
+}
+
 // r = phi * std(nc) / std(nu + g*(nc - nu)) + (1 - phi) over the one sample of
 // the [2,C,h,w] CFG pair -> fp32 [1]; two launches, the same bits on every run
 at::Tensor guidance_rescale_factor(const at::Tensor& noise, double g, double phi) {
@@ -770,6 +814,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("tokens_add_nchw", &tokens_add_nchw,
           "y [N, HW, C] + residual [N, C, H, W] -> [N, C, H, W] (transposing residual add)");
     m.def("geglu", &geglu, "a * gelu(gate) over last-dim halves");
+    m.def("geglu_linear", &geglu_linear,
+          "GEGLU projection in one MFMA GEMM: (x.Wv + bv) * gelu(x.Wg + bg), one rounding",
+          py::arg("x"), py::arg("packed"), py::arg("bias"), py::arg("inner"));
     m.def("gn_merge_stats", &gn_merge_stats,
           "merge stale peer GN moments with fresh local ones (one launch)");
     m.def("guidance_rescale_factor", &guidance_rescale_factor,

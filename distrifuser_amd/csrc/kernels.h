@@ -59,6 +59,28 @@ void launch_gn_merge_stats(void* buffer, int64_t row_stride, int64_t slot_off,
 void launch_geglu(const void* in, void* out, int64_t rows, int64_t inner, int dtype,
                   hipStream_t stream);
 
+// ---- fused GEGLU projection (geglu_linear.hip; bf16 or fp16) ------------------
+// out[r][i] = round16((x[r].W[i] + b[i]) * gelu(x[r].W[inner+i] + b[inner+i])),
+// fp32 accumulation, bias and gelu, one rounding. x: rows of K elements, ld
+// elements apart (ld >= K, K % 8 == 0, ld % 8 == 0, 128 * ld * 2 < 2^31);
+// bias [2*inner]; out [rows][inner] contiguous, inner % 8 == 0; x, wp and out
+// 16-byte aligned, bias 8-byte aligned. wp: the weight [2*inner][K] as the LDS
+// image of its A fragments, geglu_linear_packed_numel(K, inner) elements
+// [ceil(inner/128)][ceil(K/64)*4][8][64][8]: fragment f = vg*4 + sub of k16
+// slice kk of column tile ct holds, in lane l, row vg*inner + ct*128 + sub*32 +
+// (l&31), k = kk*16 + (l>>5)*8 + j; zero beyond inner and K.
+struct GegluLinearParams {
+    const uint16_t* x;
+    const uint16_t* wp;
+    const uint16_t* bias;
+    uint16_t* out;
+    int64_t rows, ld;
+    int K, inner;
+    int nks, nct;  // set by the launcher
+};
+int64_t geglu_linear_packed_numel(int K, int inner);
+void launch_geglu_linear(GegluLinearParams p, int dtype, hipStream_t stream);
+
 // ---- inpaint blend of a masked scheduler step -------------------------------
 // known = sa*init + sb*init_noise; out = m*x' + (1 - m)*known, in fp32, rounded
 // once. init and init_noise: fp32 [C*hw], one value per latent element; mask:

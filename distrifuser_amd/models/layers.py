@@ -67,14 +67,33 @@ class PlainCrossAttention(nn.Module):
 class FeedForward(nn.Module):
     """GEGLU MLP: Linear(dim -> 2*mult*dim), a*gelu(gate), Linear(mult*dim -> dim)."""
 
-    def __init__(self, dim: int, mult: int = 4):
+    def __init__(self, dim: int, mult: int = 4, *, config=None):
         super().__init__()
         inner = dim * mult
+        self.config = config  # DistriConfig: the ff_fused knob (None: off)
         self.proj_in = nn.Linear(dim, inner * 2)
         self.proj_out = nn.Linear(inner, dim)
+        self._wp = None
+        self._wp_key = None
+
+    def packed_weight(self) -> torch.Tensor:
+        """proj_in.weight in the fused kernel's layout, cached until the
+        weight storage changes (as NativeConv2d.packed_weight)."""
+        w = self.proj_in.weight
+        key = (w._version, w.data_ptr(), w.dtype, w.device)
+        if self._wp is None or self._wp_key != key:
+            with torch.no_grad():
+                self._wp = ops.pack_geglu_weight(w.detach())
+            self._wp_key = key
+        return self._wp
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return self.proj_out(ops.geglu(self.proj_in(x)))
+        if self.config is None or not self.config.ff_fused:
+            return self.proj_out(ops.geglu(self.proj_in(x)))
+        w = self.proj_in.weight
+        native = ops.use_hip(x) and w.dtype in (torch.bfloat16, torch.float16)
+        packed = self.packed_weight() if native else None
+        return self.proj_out(ops.geglu_linear(x, w, self.proj_in.bias, packed=packed))
 
 
 class LayerFactory:
@@ -136,4 +155,4 @@ class LayerFactory:
     def feed_forward(self, dim: int, mult: int = 4) -> nn.Module:
         if self.parallelism == "tensor" and self.state.config.n_device_per_batch > 1:
             return TPFeedForward(dim, mult, state=self.state)
-        return FeedForward(dim, mult)
+        return FeedForward(dim, mult, config=self.state.config)

@@ -16,6 +16,7 @@ from .dispatch import (
     flash_attention,
     flash_attention_chunked,
     geglu,
+    geglu_linear,
     group_norm_apply,
     group_norm_silu,
     group_norm_stats,
@@ -28,6 +29,7 @@ from .dispatch import (
     masked_dpm_step,
     merge_attention,
     merge_heads,
+    pack_geglu_weight,
     philox_normal,
     split_heads,
     tokens_add_nchw,
@@ -48,6 +50,7 @@ __all__ = [
     "flash_attention",
     "flash_attention_chunked",
     "geglu",
+    "geglu_linear",
     "group_norm_apply",
     "group_norm_silu",
     "group_norm_stats",
@@ -60,6 +63,7 @@ __all__ = [
     "merge_attention",
     "merge_heads",
     "pack_conv3x3_weight",
+    "pack_geglu_weight",
     "philox_normal",
     "split_heads",
     "tokens_add_nchw",

@@ -460,3 +460,70 @@ def geglu(hidden: torch.Tensor) -> torch.Tensor:
     if use_hip(hidden):
         return hip_ext().geglu(hidden)
     return eager.geglu(hidden)
+
+
+_GL_NT, _GL_KSTEP = 128, 64  # csrc/geglu_linear.hip: outputs per block, k per LDS stage
+
+
+def pack_geglu_weight(weight: torch.Tensor, dtype: torch.dtype | None = None) -> torch.Tensor:
+    """[2*inner, K] (value rows, then gate rows) -> [CT, KP/16, 8, 64, 8] in
+    dtype (default: the weight's): the geglu_linear kernel's LDS image.
+
+    Column tile ct (128 outputs), 16-k slice kk, fragment f = vg*4 + sub (vg 0
+    value / 1 gate, sub the 32-output sub-tile) holds in lane l the A operand
+    of mfma_f32_32x32x16: row vg*inner + ct*128 + sub*32 + (l&31), k = kk*16 +
+    (l>>5)*8 + j. A K-step of 64 is four consecutive slices, 32 KiB with value
+    and gate interleaved. inner is zero-padded to a multiple of 128, K to 64.
+    """
+    dtype = weight.dtype if dtype is None else dtype
+    if dtype not in _KERNEL_DTYPES:
+        raise ValueError(f"pack_geglu_weight: dtype must be bf16 or fp16, got {dtype}")
+    two_inner, k = weight.shape
+    inner = two_inner // 2
+    if two_inner != 2 * inner:
+        raise ValueError(f"pack_geglu_weight: weight must be [2*inner, K], got {tuple(weight.shape)}")
+    n_p = -(-inner // _GL_NT) * _GL_NT
+    k_p = -(-k // _GL_KSTEP) * _GL_KSTEP
+    wp = weight.new_zeros(2, n_p, k_p, dtype=dtype)
+    wp[:, :inner, :k] = weight.detach().reshape(2, inner, k).to(dtype)
+    wp = wp.reshape(2, n_p // _GL_NT, 4, 32, k_p // 16, 2, 8)  # [vg, ct, sub, r, kk, hi, j]
+    wp = wp.permute(1, 4, 0, 2, 5, 3, 6)                        # [ct, kk, vg, sub, hi, r, j]
+    return wp.reshape(n_p // _GL_NT, k_p // 16, 8, 64, 8).contiguous()
+
+
+def _geglu_linear_ok(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> bool:
+    k = x.shape[-1]
+    rows_ok = x.is_contiguous() or (
+        x.dim() == 2 and x.stride(1) == 1 and x.stride(0) >= k and x.stride(0) % 8 == 0
+    )
+    return (
+        x.dtype in _KERNEL_DTYPES
+        and weight.dtype == x.dtype
+        and bias.dtype == x.dtype
+        and x.numel() > 0
+        and k % 8 == 0
+        and weight.shape[0] % 16 == 0
+        and rows_ok
+        and x.stride(-1) == 1
+        and x.data_ptr() % 16 == 0
+    )
+
+
+def geglu_linear(x, weight, bias, packed=None):
+    """The GEGLU projection in one kernel: x [..., K], weight [2*inner, K]
+    (value rows first, gate rows second: ``nn.Linear``'s layout), bias
+    [2*inner] -> [..., inner],
+
+        out = round((x.W[:inner] + b[:inner]) * gelu(x.W[inner:] + b[inner:]))
+
+    16-bit products summed in fp32, fp32 bias and erf gelu, one rounding (the
+    rule is ``eager.geglu_linear``). On GPU, bf16 or fp16 throughout, K % 8 ==
+    0, inner % 8 == 0 and contiguous rows run the gfx950 MFMA kernel on
+    ``packed`` (``pack_geglu_weight(weight)``, packed here when not given);
+    CPU, DFA_FORCE_EAGER=1, fp32 and every other layout run the eager rule.
+    """
+    if use_hip(x) and _geglu_linear_ok(x, weight, bias):
+        if packed is None:
+            packed = pack_geglu_weight(weight)
+        return hip_ext().geglu_linear(x, packed, bias, weight.shape[0] // 2)
+    return eager.geglu_linear(x, weight, bias)

@@ -256,6 +256,16 @@ def geglu(hidden: torch.Tensor) -> torch.Tensor:
     return a * F.gelu(b)
 
 
+def geglu_linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """The fused GEGLU projection's rule: weight [2*inner, K] holds the value
+    rows, then the gate rows. fp32 matmul, fp32 bias, fp32 erf gelu and ONE
+    rounding to x's dtype (the unfused ``geglu(F.linear(x, weight, bias))``
+    rounds the projection first)."""
+    h = x.float() @ weight.float().t() + bias.float()
+    a, g = h.chunk(2, dim=-1)
+    return (a * F.gelu(g)).to(x.dtype)
+
+
 def layer_norm(x, weight, bias, eps):
     import torch.nn.functional as _F
 

@@ -66,6 +66,15 @@ def _parse_attn_dtype(value) -> str | None:
     raise ValueError(f"attn_dtype must be None or 'fp8', got {value!r}")
 
 
+def _parse_ff_fused(value) -> bool:
+    """A bool, or "1" / "0" from the environment (an empty string is off)."""
+    if isinstance(value, bool):
+        return value
+    if isinstance(value, str) and value.strip() in ("", "0", "1"):
+        return value.strip() == "1"
+    raise ValueError(f"ff_fused must be a bool (DFA_FF_FUSED: '1' or '0'), got {value!r}")
+
+
 def is_power_of_2(n: int) -> bool:
     return n >= 1 and (n & (n - 1)) == 0
 
@@ -104,6 +113,7 @@ class DistriConfig:
         device: str | torch.device | None = None,
         attn_kv_splits: int | str = _ATTN_KV_SPLITS_UNSET,
         attn_dtype: str | None = None,
+        ff_fused: bool | None = None,
     ):
         # Self-attention split-KV: a positive int, or "auto" for
         # ops.attention_kv_splits per call site. Left at its default (1), the
@@ -117,6 +127,12 @@ class DistriConfig:
         if attn_dtype is None:
             attn_dtype = os.environ.get("DFA_ATTN_DTYPE")
         self.attn_dtype = _parse_attn_dtype(attn_dtype)
+        # Feed-forward GEGLU projection: False is the hipBLASLt GEMM followed by
+        # the gate kernel, True the one fused MFMA kernel (ops.geglu_linear).
+        # Left at None, the DFA_FF_FUSED environment variable takes its place.
+        if ff_fused is None:
+            ff_fused = os.environ.get("DFA_FF_FUSED", "0")
+        self.ff_fused = _parse_ff_fused(ff_fused)
         assert mode in VALID_MODES, f"mode must be one of {VALID_MODES}, got {mode!r}"
         assert parallelism in VALID_PARALLELISM, (
             f"parallelism must be one of {VALID_PARALLELISM}, got {parallelism!r}"

@@ -4,7 +4,8 @@ Run on an MI355X: python scripts/kernel_bench.py > gpurun_out/kernel_bench.json
 (--splitkv-only: just the split-KV attention sweep; --vae-downsample-only:
 just the VAE-encoder downsample convs; --rescale-only: just the rescaled
 DDIM step, native against the torch composition; --fp8-only: the e4m3
-attention path against the 16-bit kernel; --dtype {bf16,fp16}: the
+attention path against the 16-bit kernel; --ff-only: the fused GEGLU
+projection against F.linear + ops.geglu, both dtypes; --dtype {bf16,fp16}: the
 element type of the attention, conv, LayerNorm and VAE-attention rows, default
 bf16 — fp16 rows carry "dtype": "fp16")
 """
@@ -77,6 +78,45 @@ def splitkv_sweep(results, reps=5, iters=100):
             row[f"spread_{name}"] = [t[0], t[-1]]
         results.append(row)
         print(json.dumps(row), flush=True)
+
+
+def ff_rows(results, reps=5, iters=10):
+    """ops.geglu_linear (one MFMA kernel on the packed weight) against
+    ops.geglu(F.linear(x, w, b)) (hipBLASLt, then the gate kernel) at the
+    feed-forward shapes of the 3840^2 step and its eighth-size patches, bf16
+    and fp16. Both warmed, interleaved `reps` times; median and min..max, the
+    FLOP/s of the 2 * rows * K * 2 * inner product, rel-L2 of the two outputs."""
+    from distrifuser_amd import ops
+
+    dev = "cuda:0"
+    ext = ops.hip_ext()
+    shapes = [(115200, 640, 2560), (28800, 1280, 5120), (14400, 640, 2560), (3600, 1280, 5120)]
+    for dt, name in ((torch.bfloat16, "bf16"), (torch.float16, "fp16")):
+        for rows, k, inner in shapes:
+            x = torch.randn(rows, k, device=dev, dtype=dt)
+            w = (torch.randn(2 * inner, k, device=dev) * k ** -0.5).to(dt)
+            b = torch.randn(2 * inner, device=dev, dtype=dt)
+            packed = ops.pack_geglu_weight(w)
+            fns = {"fused": lambda: ext.geglu_linear(x, packed, b, inner),
+                   "unfused": lambda: ops.geglu(F.linear(x, w, b))}
+            got, ref = fns["fused"]().float(), fns["unfused"]().float()
+            ms = {n: [] for n in fns}
+            for n in fns:
+                timeit(fns[n], iters=3, warmup=2)
+            for _ in range(reps):
+                for n in fns:
+                    ms[n].append(timeit(fns[n], iters=iters, warmup=1))
+            flops = 2.0 * rows * k * 2 * inner
+            row = {"op": "geglu_linear", "dtype": name, "rows": rows, "K": k, "inner": inner,
+                   "reps": reps, "rel_l2": ((got - ref).norm() / ref.norm()).item()}
+            for n in fns:
+                t = sorted(ms[n])
+                row[f"ms_{n}"] = t[len(t) // 2]
+                row[f"spread_{n}"] = [t[0], t[-1]]
+                row[f"tflops_{n}"] = flops / t[len(t) // 2] / 1e9
+            results.append(row)
+            print(json.dumps(row), flush=True)
+            del x, w, b, packed, got, ref
 
 
 def fp8_attention_rows(results, dt, tag, reps=5, iters=30):
@@ -229,6 +269,10 @@ def main():
 
     if "--fp8-only" in sys.argv[1:]:
         fp8_attention_rows(results, dt, tag)
+        return 0
+
+    if "--ff-only" in sys.argv[1:]:
+        ff_rows(results)
         return 0
 
     if "--rescale-only" in sys.argv[1:]:

@@ -22,6 +22,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "bindings.hip"),
         os.path.join(CSRC, "groupnorm.hip"),
         os.path.join(CSRC, "geglu.hip"),
+        os.path.join(CSRC, "geglu_linear.hip"),
         os.path.join(CSRC, "scheduler.hip"),
         os.path.join(CSRC, "attention.hip"),
         os.path.join(CSRC, "attention_fp8.hip"),
