@@ -666,6 +666,78 @@ at::Tensor conv3x3(const at::Tensor& x, const at::Tensor& wp,
     return o;
 }
 
+// 2x nearest upsample + 3x3 pad-1 conv on collapsed weights -> [B, cout, 2H, 2W]
+at::Tensor upsample2x_conv3x3(const at::Tensor& x, const at::Tensor& wp,
+                              const c10::optional<at::Tensor>& bias, int64_t cout,
+                              const c10::optional<at::Tensor>& top,
+                              const c10::optional<at::Tensor>& bot) {
+    constexpr const char* op = "upsample2x_conv3x3";
+    TORCH_CHECK(x.is_cuda() && x.dim() == 4 && is_b16(x), op,
+                ": x must be CUDA bf16 or fp16 [B,Cin,H,W]");
+    TORCH_CHECK(x.numel() > 0 && cout > 0, op, ": empty input or cout");
+    const auto dt = x.scalar_type();
+    const int64_t B = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
+    TORCH_CHECK(x.stride(3) == 1 && x.stride(2) == W, op, ": x rows must be contiguous");
+    TORCH_CHECK(x.stride(0) >= 0 && x.stride(1) >= H * W, op,
+                ": x channel planes must not overlap");
+    TORCH_CHECK(wp.is_cuda() && wp.dim() == 5 && wp.is_contiguous() && wp.size(0) == 16 &&
+                    wp.size(3) == 64 && wp.size(4) == 8,
+                op, ": packed must be pack_upsample2x_conv3x3_weight's [16][KS][CT][64][8]");
+    TORCH_CHECK(wp.scalar_type() == dt, op, ": packed must have x's dtype (", dt, "), got ",
+                wp.scalar_type());
+    TORCH_CHECK(wp.size(1) * 16 >= Cin && wp.size(2) * 32 >= cout, op,
+                ": packed weight too small for Cin ", Cin, ", cout ", cout);
+    TORCH_CHECK(((Cin + 63) * x.stride(1) + H * W) * 2 < (int64_t(1) << 31) &&
+                    4 * H * W < (int64_t(1) << 31),
+                op, ": one batch element of x must stay below 2 GiB");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 2 == 0 &&
+                    reinterpret_cast<uintptr_t>(wp.data_ptr()) % 16 == 0,
+                op, ": x must be 2-byte and packed 16-byte aligned");
+
+    ConvUp2xParams p{};
+    p.x = reinterpret_cast<const uint16_t*>(x.data_ptr());
+    p.wp = reinterpret_cast<const uint16_t*>(wp.data_ptr());
+    p.B = (int)B;
+    p.Cin = (int)Cin;
+    p.Cout = (int)cout;
+    p.H = (int)H;
+    p.W = (int)W;
+    p.KS = (int)wp.size(1);
+    p.CT = (int)wp.size(2);
+    p.x_sb = x.stride(0);
+    p.x_sc = x.stride(1);
+    // 16-byte row loads where every row starts on 16 bytes, else 2-byte loads
+    p.vec = W % 8 == 0 && reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 &&
+            p.x_sb % 8 == 0 && p.x_sc % 8 == 0;
+    at::Tensor bias_c;
+    if (bias.has_value()) {
+        bias_c = b16_param(*bias, x, op, "bias");
+        TORCH_CHECK(bias_c.numel() == cout, op, ": bias must have ", cout, " elements");
+        p.bias = reinterpret_cast<const uint16_t*>(bias_c.data_ptr());
+    }
+    auto set_halo = [&](const c10::optional<at::Tensor>& h, const uint16_t*& ptr, int64_t& sb,
+                        int64_t& sc) {
+        if (!h.has_value()) return;
+        const at::Tensor& t = *h;
+        TORCH_CHECK(t.scalar_type() == dt, op, ": top/bot halo must have x's dtype (", dt,
+                    "), got ", t.scalar_type());
+        TORCH_CHECK(t.is_cuda() && (t.dim() == 3 || (t.dim() == 4 && t.size(2) == 1)) &&
+                        t.stride(-1) == 1 && t.size(-1) == W && t.size(1) == Cin &&
+                        t.size(0) == B,
+                    op, ": halo must be [B,Cin,(1,)W] with contiguous rows");
+        ptr = reinterpret_cast<const uint16_t*>(t.data_ptr());
+        sb = t.stride(0);
+        sc = t.stride(1);
+    };
+    set_halo(top, p.top, p.t_sb, p.t_sc);
+    set_halo(bot, p.bot, p.b_sb, p.b_sc);
+
+    auto o = at::empty({B, cout, 2 * H, 2 * W}, x.options());
+    p.o = reinterpret_cast<uint16_t*>(o.data_ptr());
+    launch_conv_up2x(p, dtype_of(x), cur_stream());
+    return o;
+}
+
 // -> (prev, x0 fp32); prev alone takes a's noise and blend
 std::vector<at::Tensor> dpm_step(StepArgs a, const c10::optional<at::Tensor>& x0_prev, double cc,
                                  double cx, double ce) {
@@ -873,6 +945,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           pybind11::arg("x"), pybind11::arg("wp"), pybind11::arg("bias"), pybind11::arg("cout"), pybind11::arg("stride"),
           pybind11::arg("top"), pybind11::arg("bot"), pybind11::arg("residual"), pybind11::arg("bias2"),
           pybind11::arg("pad_lo") = 1);
+    m.def("upsample2x_conv3x3", &upsample2x_conv3x3,
+          "bf16/fp16 2x nearest upsample + 3x3 pad-1 conv in one kernel, collapsed packed weights, "
+          "halo rows at input resolution",
+          pybind11::arg("x"), pybind11::arg("packed"), pybind11::arg("bias"), pybind11::arg("cout"),
+          pybind11::arg("top") = pybind11::none(), pybind11::arg("bot") = pybind11::none());
     m.def("mfma_probe", &mfma_probe, "dump mfma_f32_16x16x32_bf16 fragment mapping");
     m.def("mfma_probe32", &mfma_probe32, "dump mfma_f32_32x32x16_bf16 fragment mapping");
     m.def("mfma_probe_fp8", &mfma_probe_fp8,

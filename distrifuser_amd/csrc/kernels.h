@@ -187,6 +187,31 @@ struct Conv3x3Params {
 // dtype: DFA_BF16 or DFA_F16 for x, halos, wp, bias, residual, bias2 and o alike
 void launch_conv3x3(const Conv3x3Params& p, int stride, int dtype, hipStream_t stream);
 
+// ---- 2x nearest upsample + 3x3 pad-1 conv in one kernel (conv_up2x.hip) -------------
+// o[b][co][2y+py][2x+px] = round16(bias[co] + sum_{a,b,ci} Wc[py][px][a][b][co][ci] *
+// x[b][ci][y+a+py-1][x+b+px-1]), fp32 accumulation; rows -1 / H read top / bot
+// (null: zero), columns -1 / W are zero. x, top, bot, bias as in Conv3x3Params,
+// at INPUT resolution; o: [B][Cout][2H][2W] contiguous, 4-byte aligned.
+// wp: the collapsed weights in A-fragment order [4 parities][4 taps][KS][CT][64][8],
+// parity = py*2 + px, tap = a*2 + b, lane map and zero padding as conv3x3's wp.
+// vec: 16-byte row loads; needs W % 8 == 0, x 16-byte aligned and x_sb, x_sc
+// multiples of 8. ((Cin + 63) * x_sc + H * W) * 2 must stay below 2^31.
+struct ConvUp2xParams {
+    const uint16_t* x;
+    const uint16_t* top;
+    const uint16_t* bot;
+    const uint16_t* wp;
+    const uint16_t* bias;
+    uint16_t* o;
+    int B, Cin, Cout, H, W;
+    int KS, CT;
+    int vec;
+    int64_t x_sb, x_sc;
+    int64_t t_sb, t_sc;
+    int64_t b_sb, b_sc;
+};
+void launch_conv_up2x(const ConvUp2xParams& p, int dtype, hipStream_t stream);
+
 // ---- fused (residual +) LayerNorm (bf16 or fp16, C <= 2048, C % 8 == 0) -------------
 // y = LN(x [+ res]); when res != null and sum_out != null, x+res is also
 // written to sum_out (the transformer residual add fused away).

@@ -120,8 +120,13 @@ class Upsample2D(nn.Module):
     def __init__(self, channels: int, *, factory: LayerFactory):
         super().__init__()
         self.conv = factory.conv2d(channels, channels, 3, stride=1, padding=1, tp_shard=True)
+        self.config = factory.state.config  # DistriConfig: the upsample_fused knob
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self.config.upsample_fused:
+            # one op on the input grid (ops.upsample2x_conv3x3); the displaced-
+            # patch conv, whose halo rows are upsampled rows, keeps the two ops
+            return self.conv.upsample2x(x)
         # Nearest-neighbour 2x is purely row-local, so it composes with row
         # patching with no extra communication.
         x = F.interpolate(x, scale_factor=2.0, mode="nearest")

@@ -123,17 +123,21 @@ class VAEAttention(nn.Module):
 
 
 class UpDecoderBlock2D(nn.Module):
-    def __init__(self, in_ch: int, out_ch: int, layers: int, add_upsample: bool, groups: int):
+    def __init__(self, in_ch: int, out_ch: int, layers: int, add_upsample: bool, groups: int,
+                 upsample_fused: bool = False):
         super().__init__()
         self.resnets = nn.ModuleList(
             [VAEResnetBlock(in_ch if i == 0 else out_ch, out_ch, groups) for i in range(layers)]
         )
         self.upsampler = NativeConv2d(out_ch, out_ch, 3, padding=1) if add_upsample else None
+        self.upsample_fused = upsample_fused  # DistriConfig.upsample_fused
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         for r in self.resnets:
             x = r(x)
-        if self.upsampler is not None:
+        if self.upsampler is not None and self.upsample_fused:
+            x = self.upsampler.upsample2x(x)  # ops.upsample2x_conv3x3
+        elif self.upsampler is not None:
             x = F.interpolate(x, scale_factor=2.0, mode="nearest")
             x = self.upsampler(x)
         return x
@@ -223,7 +227,9 @@ class _TilingMixin:
 
 
 class VAEDecoder(_TilingMixin, nn.Module):
-    def __init__(self, config: VAEDecoderConfig):
+    def __init__(self, config: VAEDecoderConfig, upsample_fused: bool = False):
+        """upsample_fused: DistriConfig.upsample_fused, the upsample stages as
+        one fused op each (off: interpolate + conv)."""
         super().__init__()
         self.config = config
         ch = config.block_out_channels
@@ -242,6 +248,7 @@ class VAEDecoder(_TilingMixin, nn.Module):
                 UpDecoderBlock2D(
                     prev, out_ch, config.layers_per_block + 1,
                     add_upsample=i < len(rev) - 1, groups=groups,
+                    upsample_fused=upsample_fused,
                 )
             )
             prev = out_ch

@@ -7,7 +7,13 @@ runs, which is what the non-GPU test suite checks numerics against.
 Set DFA_FORCE_EAGER=1 to force the eager path on GPU (A/B debugging only).
 """
 
-from .conv import NativeConv2d, conv3x3_halo, pack_conv3x3_weight
+from .conv import (
+    NativeConv2d,
+    conv3x3_halo,
+    pack_conv3x3_weight,
+    pack_upsample2x_conv3x3_weight,
+    upsample2x_conv3x3,
+)
 from .dispatch import (
     add_layer_norm,
     attention_kv_splits,
@@ -64,9 +70,11 @@ __all__ = [
     "merge_heads",
     "pack_conv3x3_weight",
     "pack_geglu_weight",
+    "pack_upsample2x_conv3x3_weight",
     "philox_normal",
     "split_heads",
     "tokens_add_nchw",
+    "upsample2x_conv3x3",
     "use_hip",
     "vae_attention",
 ]

@@ -85,6 +85,53 @@ def conv3x3_halo(x, weight, bias, stride=1, top=None, bot=None, packed=None, res
     return out if residual is None else out + residual
 
 
+def pack_upsample2x_conv3x3_weight(weight: torch.Tensor,
+                                   dtype: torch.dtype | None = None) -> torch.Tensor:
+    """[Cout, Cin, 3, 3] -> [16, KS, CT, 64, 8]: the collapsed weights of the
+    fused upsample conv (``eager.collapse_upsample2x_weight``: fp32 sums of the
+    16-bit taps, rounded once) in A-fragment order, as bf16 (dtype None) or fp16.
+
+    Slice (py*2 + px)*4 + a*2 + b holds the 2x2 kernel tap (a, b) of output
+    parity (py, px); within it the lane map and the zero padding (Cin to 64,
+    Cout to 32) are those of :func:`pack_conv3x3_weight`.
+    """
+    dtype = torch.bfloat16 if dtype is None else dtype
+    if dtype not in _CONV_DTYPES:
+        raise ValueError(f"pack_upsample2x_conv3x3_weight: dtype must be bf16 or fp16, got {dtype}")
+    cout, cin, kh, kw = weight.shape
+    assert kh == 3 and kw == 3, "pack_upsample2x_conv3x3_weight is 3x3 only"
+    wc = eager.collapse_upsample2x_weight(weight, dtype).reshape(16, cout, cin)
+    cin_p = (cin + 63) // 64 * 64
+    cout_p = (cout + 31) // 32 * 32
+    wp = wc.new_zeros(16, cout_p, cin_p)
+    wp[:, :cout, :cin] = wc
+    ks, ct = cin_p // 16, cout_p // 32
+    wp = wp.reshape(16, ct, 32, ks, 2, 8)  # cout = ct*32 + r, cin = ks*16 + hi*8 + j
+    wp = wp.permute(0, 3, 1, 4, 2, 5)      # [16][ks][ct][hi][r][j]
+    return wp.reshape(16, ks, ct, 64, 8).contiguous()
+
+
+def upsample2x_conv3x3(x, weight, bias, top=None, bot=None, packed=None):
+    """2x nearest upsample then the pad-1 3x3 conv, as ONE op on the input
+    grid: x [B, Cin, H, W] -> [B, Cout, 2H, 2W]; the upsampled tensor is never
+    written. ``top`` / ``bot`` are single halo rows at INPUT resolution
+    [B, Cin, 1, W] (None: zero padding). The rule, collapsed weights rounded
+    once to 16 bits included, is ``eager.upsample2x_conv3x3``.
+
+    bf16 / fp16 GPU inputs with contiguous rows (the test of
+    :func:`conv3x3_halo`) run the gfx950 kernel on ``packed``
+    (:func:`pack_upsample2x_conv3x3_weight`, packed here when not given); CPU,
+    DFA_FORCE_EAGER=1 and every other input run the eager rule."""
+    if use_hip(x) and _hip_conv_ok(x, 1) and weight.dtype == x.dtype:
+        t = top.reshape(top.shape[0], top.shape[1], -1) if top is not None else None
+        b = bot.reshape(bot.shape[0], bot.shape[1], -1) if bot is not None else None
+        if (t is None or t.stride(-1) == 1) and (b is None or b.stride(-1) == 1):
+            if packed is None:
+                packed = pack_upsample2x_conv3x3_weight(weight, x.dtype)
+            return hip_ext().upsample2x_conv3x3(x, packed, bias, weight.shape[0], t, b)
+    return eager.upsample2x_conv3x3(x, weight, bias, top, bot)
+
+
 class NativeConv2d(nn.Conv2d):
     """nn.Conv2d that rides the gfx950 implicit-GEMM kernel on GPU.
 
@@ -106,6 +153,8 @@ class NativeConv2d(nn.Conv2d):
         self.asym_pad = asym_pad
         self._wp = None
         self._wp_key = None
+        self._wp_up2x = None
+        self._wp_up2x_key = None
 
     def _native_eligible(self, x: torch.Tensor) -> bool:
         return (
@@ -129,6 +178,33 @@ class NativeConv2d(nn.Conv2d):
                     w.detach(), torch.float16 if w.dtype == torch.float16 else None)
             self._wp_key = key
         return self._wp
+
+    def packed_upsample2x_weight(self) -> torch.Tensor:
+        """The collapsed weight of :meth:`upsample2x`, cached like packed_weight."""
+        w = self.weight
+        key = (w._version, w.data_ptr(), w.dtype, w.device)
+        if self._wp_up2x is None or self._wp_up2x_key != key:
+            with torch.no_grad():
+                self._wp_up2x = pack_upsample2x_conv3x3_weight(w.detach(), w.dtype)
+            self._wp_up2x_key = key
+        return self._wp_up2x
+
+    def upsample2x(self, x: torch.Tensor, top=None, bot=None) -> torch.Tensor:
+        """This conv (3x3, stride 1, padding 1) applied to the 2x nearest
+        upsample of x, as ``upsample2x_conv3x3``: one kernel on GPU, and the
+        same rule (collapsed, once-rounded weights) on every other path.
+        top / bot are halo rows at x's resolution."""
+        if not (self.kernel_size == (3, 3) and self.stride == (1, 1) and self.padding == (1, 1)
+                and self.dilation == (1, 1) and self.groups == 1):
+            raise ValueError("upsample2x needs a 3x3 conv with stride 1 and padding 1")
+        packed = None
+        if use_hip(x) and x.dtype in _CONV_DTYPES and self.weight.dtype == x.dtype:
+            if not _hip_conv_ok(x, 1):
+                x = x.contiguous()
+            packed = self.packed_upsample2x_weight()
+        from . import upsample2x_conv3x3 as op  # the public name: one place to intercept
+
+        return op(x, self.weight, self.bias, top, bot, packed=packed)
 
     def forward(self, x: torch.Tensor, top=None, bot=None, residual=None,
                 bias2=None) -> torch.Tensor:

@@ -511,3 +511,62 @@ def conv3x3_halo(
     # pad-1 stride-s output has ceil(H/s) rows regardless of halo presence
     ho = (h - 1) // stride + 1
     return out[:, :, :ho, :]
+
+
+# 3x3 rows (or columns) that land on input row y + a + p - 1 for output parity p:
+# _UP2X_TAPS[p][a]
+_UP2X_TAPS = (((0,), (1, 2)), ((0, 1), (2,)))
+
+
+def collapse_upsample2x_weight(weight: torch.Tensor, dtype: torch.dtype | None = None) -> torch.Tensor:
+    """[Cout, Cin, 3, 3] -> Wc [2, 2, 2, 2, Cout, Cin] = [py][px][a][b]: the
+    2x2 kernels, one per output parity, that a 2x nearest upsample followed by
+    the pad-1 3x3 conv amounts to on the input grid. Taps that land on one input
+    pixel are added: the weight is taken in ``dtype`` (default: its own),
+    summed in fp32 (float64 for a float64 weight) and rounded once to dtype."""
+    dtype = weight.dtype if dtype is None else dtype
+    acc = torch.float64 if dtype == torch.float64 else torch.float32
+    w = weight.detach().to(dtype).to(acc)
+    cout, cin = w.shape[:2]
+    wc = w.new_zeros(2, 2, 2, 2, cout, cin)
+    for py in range(2):
+        for px in range(2):
+            for a in range(2):
+                for b in range(2):
+                    for dy in _UP2X_TAPS[py][a]:
+                        for dx in _UP2X_TAPS[px][b]:
+                            wc[py, px, a, b] += w[:, :, dy, dx]
+    return wc.to(dtype)
+
+
+def upsample2x_conv3x3(
+    x: torch.Tensor,
+    weight: torch.Tensor,
+    bias: torch.Tensor | None,
+    top: torch.Tensor | None = None,
+    bot: torch.Tensor | None = None,
+) -> torch.Tensor:
+    """The rule of the fused 2x nearest upsample + pad-1 3x3 conv (the
+    conv_up2x kernel): x [B, Cin, H, W] -> [B, Cout, 2H, 2W].
+
+    Output pixel (2y+py, 2x+px) is a 2x2 conv on the input grid with the
+    collapsed weights of :func:`collapse_upsample2x_weight` (rounded to the
+    weight's dtype: the one difference to interpolate + conv), tap (a, b)
+    reading input (y+a+py-1, x+b+px-1). fp32 products and sums (float64 for
+    float64 inputs), fp32 bias, one rounding to x's dtype. top / bot: the
+    neighbour patch's last / first INPUT row [B, Cin, 1, W] at rows -1 / H;
+    None is zero padding, as are columns -1 and W."""
+    bsz, c, h, w = x.shape
+    acc = torch.float64 if x.dtype == torch.float64 else torch.float32
+    wc = collapse_upsample2x_weight(weight).to(acc)
+    rows = [x.new_zeros(bsz, c, 1, w) if t is None else t.reshape(bsz, c, 1, w)
+            for t in (top, bot)]
+    xp = F.pad(torch.cat([rows[0], x, rows[1]], dim=2).to(acc), [1, 1, 0, 0])
+    out = x.new_empty(bsz, weight.shape[0], 2 * h, 2 * w)
+    for py in range(2):
+        for px in range(2):
+            k = wc[py, px].permute(2, 3, 0, 1)  # [Cout, Cin, a, b]
+            r = F.conv2d(xp[:, :, py : py + h + 1, px : px + w + 1], k,
+                         None if bias is None else bias.to(acc))
+            out[:, :, py::2, px::2] = r.to(x.dtype)
+    return out

@@ -178,6 +178,14 @@ class PatchConv2d(nn.Module):
         # pointers, SURVEY K4 — no cat, no boundary-row recompute pass)
         return conv(x, top=top, bot=bot, residual=residual, bias2=bias2)
 
+    def upsample2x(self, x: torch.Tensor) -> torch.Tensor:
+        """This conv on the 2x nearest upsample of x. One device: the fused
+        op. Patch parallel: the exchanged halo rows are rows of the UPSAMPLED
+        tensor, so that path stays interpolate + conv."""
+        if not _is_patch_parallel(self.state):
+            return self.conv.upsample2x(x)
+        return self.forward(F.interpolate(x, scale_factor=2.0, mode="nearest"))
+
     def forward(self, x: torch.Tensor, residual=None, bias2=None) -> torch.Tensor:
         if not _is_patch_parallel(self.state):
             return self.conv(x, residual=residual, bias2=bias2)

@@ -187,8 +187,13 @@ class TPConv2d(nn.Module):
         if b is not None and self.bias is not None:
             self.bias.data.copy_(b)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        out = self.conv(x[:, self.c_start : self.c_start + self.c_local])
+    def upsample2x(self, x: torch.Tensor) -> torch.Tensor:
+        """forward on the 2x nearest upsample of x, the local conv as the fused op."""
+        return self.forward(x, upsample2x=True)
+
+    def forward(self, x: torch.Tensor, upsample2x: bool = False) -> torch.Tensor:
+        x = x[:, self.c_start : self.c_start + self.c_local]
+        out = self.conv.upsample2x(x) if upsample2x else self.conv(x)
         if _tp_degree(self.state) > 1 and dist.is_initialized():
             dist.all_reduce(out, op=dist.ReduceOp.SUM, group=self.state.config.batch_group)
         if self.bias is not None:

@@ -627,7 +627,7 @@ class DistriSDXLPipeline(_DistriPipelineBase):
         unet_cfg = kwargs.pop("unet_config", unet_cfg)
 
         unet = DistriUNet(unet_cfg, distri_config)
-        vae = VAEDecoder(vae_cfg)
+        vae = VAEDecoder(vae_cfg, upsample_fused=distri_config.upsample_fused)
         te1 = CLIPTextEncoder(clip1_cfg)
         te2 = CLIPTextEncoder(clip2_cfg)
         unet, vae, te1, te2 = _DistriPipelineBase._load_components(
@@ -782,7 +782,7 @@ class DistriSDPipeline(_DistriPipelineBase):
         unet_cfg = kwargs.pop("unet_config", unet_cfg)
 
         unet = DistriUNet(unet_cfg, distri_config)
-        vae = VAEDecoder(vae_cfg)
+        vae = VAEDecoder(vae_cfg, upsample_fused=distri_config.upsample_fused)
         te = CLIPTextEncoder(clip_cfg)
         unet, vae, te = _DistriPipelineBase._load_components(
             pretrained, {"unet": unet, "vae": vae, "text_encoder": te},

@@ -75,6 +75,16 @@ def _parse_ff_fused(value) -> bool:
     raise ValueError(f"ff_fused must be a bool (DFA_FF_FUSED: '1' or '0'), got {value!r}")
 
 
+def _parse_upsample_fused(value) -> bool:
+    """A bool, or "1" / "0" from the environment (an empty string is off)."""
+    if isinstance(value, bool):
+        return value
+    if isinstance(value, str) and value.strip() in ("", "0", "1"):
+        return value.strip() == "1"
+    raise ValueError(
+        f"upsample_fused must be a bool (DFA_UPSAMPLE_FUSED: '1' or '0'), got {value!r}")
+
+
 def is_power_of_2(n: int) -> bool:
     return n >= 1 and (n & (n - 1)) == 0
 
@@ -114,6 +124,7 @@ class DistriConfig:
         attn_kv_splits: int | str = _ATTN_KV_SPLITS_UNSET,
         attn_dtype: str | None = None,
         ff_fused: bool | None = None,
+        upsample_fused: bool | None = None,
     ):
         # Self-attention split-KV: a positive int, or "auto" for
         # ops.attention_kv_splits per call site. Left at its default (1), the
@@ -133,6 +144,15 @@ class DistriConfig:
         if ff_fused is None:
             ff_fused = os.environ.get("DFA_FF_FUSED", "0")
         self.ff_fused = _parse_ff_fused(ff_fused)
+        # 2x upsample stages (U-Net Upsample2D, VAE decoder): False is
+        # F.interpolate followed by the 3x3 conv, True the one kernel on
+        # parity-collapsed weights (ops.upsample2x_conv3x3), whose once-rounded
+        # weight sums are why this is a knob. The displaced-patch path keeps
+        # the two ops either way. Left at None, the DFA_UPSAMPLE_FUSED
+        # environment variable takes its place.
+        if upsample_fused is None:
+            upsample_fused = os.environ.get("DFA_UPSAMPLE_FUSED", "0")
+        self.upsample_fused = _parse_upsample_fused(upsample_fused)
         assert mode in VALID_MODES, f"mode must be one of {VALID_MODES}, got {mode!r}"
         assert parallelism in VALID_PARALLELISM, (
             f"parallelism must be one of {VALID_PARALLELISM}, got {parallelism!r}"

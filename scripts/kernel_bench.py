@@ -5,7 +5,8 @@ Run on an MI355X: python scripts/kernel_bench.py > gpurun_out/kernel_bench.json
 just the VAE-encoder downsample convs; --rescale-only: just the rescaled
 DDIM step, native against the torch composition; --fp8-only: the e4m3
 attention path against the 16-bit kernel; --ff-only: the fused GEGLU
-projection against F.linear + ops.geglu, both dtypes; --dtype {bf16,fp16}: the
+projection against F.linear + ops.geglu, both dtypes; --up2x-only: the fused
+upsample conv against F.interpolate + conv3x3, both dtypes; --dtype {bf16,fp16}: the
 element type of the attention, conv, LayerNorm and VAE-attention rows, default
 bf16 — fp16 rows carry "dtype": "fp16")
 """
@@ -117,6 +118,51 @@ def ff_rows(results, reps=5, iters=10):
             results.append(row)
             print(json.dumps(row), flush=True)
             del x, w, b, packed, got, ref
+
+
+def up2x_rows(results, reps=5, iters=10):
+    """ext.upsample2x_conv3x3 (one kernel on the collapsed weights) against
+    F.interpolate + ext.conv3x3 on the same input, at the two largest U-Net
+    upsample convs of the 3840^2 step (CFG pair) and the largest VAE stage,
+    bf16 and fp16. Both warmed, interleaved `reps` times; median and min..max.
+    TFLOP/s of BOTH columns count the unfused 2 * B * Cout * Cin * 9 * 4HW
+    product, so their ratio is the time ratio. rel-L2 of the two outputs."""
+    from distrifuser_amd import ops
+
+    dev = "cuda:0"
+    ext = ops.hip_ext()
+    shapes = [(2, 1280, 120), (2, 640, 240), (1, 512, 480)]
+    for dt, name in ((torch.bfloat16, "bf16"), (torch.float16, "fp16")):
+        for b, c, hw in shapes:
+            x = torch.randn(b, c, hw, hw, device=dev, dtype=dt)
+            w = (torch.randn(c, c, 3, 3, device=dev) * (9 * c) ** -0.5).to(dt)
+            bias = torch.randn(c, device=dev, dtype=dt)
+            packed = ops.pack_conv3x3_weight(w, dt)
+            packed_up = ops.pack_upsample2x_conv3x3_weight(w, dt)
+            fns = {"fused": lambda: ext.upsample2x_conv3x3(x, packed_up, bias, c),
+                   "unfused": lambda: ext.conv3x3(
+                       F.interpolate(x, scale_factor=2.0, mode="nearest"), packed, bias, c, 1,
+                       None, None, None, None)}
+            got, ref = fns["fused"]().float(), fns["unfused"]().float()
+            rel_l2 = ((got - ref).norm() / ref.norm()).item()
+            del got, ref
+            ms = {n: [] for n in fns}
+            for n in fns:
+                timeit(fns[n], iters=3, warmup=2)
+            for _ in range(reps):
+                for n in fns:
+                    ms[n].append(timeit(fns[n], iters=iters, warmup=1))
+            flops = 2.0 * b * c * c * 9 * 4 * hw * hw
+            row = {"op": "upsample2x_conv3x3", "dtype": name, "B": b, "C": c, "H": hw,
+                   "reps": reps, "rel_l2": rel_l2}
+            for n in fns:
+                t = sorted(ms[n])
+                row[f"ms_{n}"] = t[len(t) // 2]
+                row[f"spread_{n}"] = [t[0], t[-1]]
+                row[f"tflops_{n}"] = flops / t[len(t) // 2] / 1e9
+            results.append(row)
+            print(json.dumps(row), flush=True)
+            del x, w, bias, packed, packed_up
 
 
 def fp8_attention_rows(results, dt, tag, reps=5, iters=30):
@@ -273,6 +319,10 @@ def main():
 
     if "--ff-only" in sys.argv[1:]:
         ff_rows(results)
+        return 0
+
+    if "--up2x-only" in sys.argv[1:]:
+        up2x_rows(results)
         return 0
 
     if "--rescale-only" in sys.argv[1:]:

@@ -27,6 +27,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "attention.hip"),
         os.path.join(CSRC, "attention_fp8.hip"),
         os.path.join(CSRC, "conv.hip"),
+        os.path.join(CSRC, "conv_up2x.hip"),
         os.path.join(CSRC, "vae_attn.hip"),
         os.path.join(CSRC, "layernorm.hip"),
     ],
